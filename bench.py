@@ -16,8 +16,9 @@ distributions as the reference's ``usage.rb``), generated on device before timin
 The records are held on device packed once at load time, losslessly (``--layout rowpacked``: the
 5 codes + one-hot class of a record in 13 bits, streamed as a dense 13-bit record stream; the
 16-bit word form is kept too) or as uint8 code columns (``--layout columns``).
-CSV parsing and packing are NOT in the timed steps (the headline is the on-device training pass);
-``extra`` reports them separately:
+CSV parsing and packing are NOT in the timed steps (the headline is the on-device training pass).
+A plain run sets up, warms up, times the steps and prints the result line; with ``--full`` it then
+also measures, in runs of their own, and reports under ``extra``:
 
 * ``columns_rows_per_s_per_gpu`` — the same training step over the uint8 code columns.
 * ``ingest`` (``--ingest-rows``; default 2^26 records on one GPU, 2^24 per rank on more) — the
@@ -28,7 +29,12 @@ CSV parsing and packing are NOT in the timed steps (the headline is the on-devic
   1 MB / 64 MB over the job's GPUs, next to the deterministic all-gather path and the hand-written
   peer-mapped one-shot / two-shot kernels (``algo="p2p"``, csrc/kernels/comm.hip).
 
+``--dump-outputs DIR`` writes the model that the last timed step fitted (count table, class counts,
+log-probability tables) as ``DIR/<name>.npy``; the records are seeded, so runs with the same
+arguments have identical inputs and two builds can be compared array for array.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows-per-gpu R] [--layout L]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -255,6 +261,21 @@ def _ingest(rows: int, schema, dev, comm) -> dict:
             os.remove(path)
 
 
+def _dump_outputs(nb, out_dir: str) -> None:
+    """What a caller of the timed step receives, the fitted model of the LAST timed step: the
+    count table and class counts (exact integers, stored as float64) and the float32
+    log-probability tables of the predictor.  A few KB; the inputs are seeded, so two builds run
+    with the same arguments can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tb = nb.tables()
+    arrays = {"counts": nb.counts.double(), "class_n": nb.class_n.double(),
+              "logp": tb["logp"].float(), "logfp": tb["logfp"].float(), "logprior": tb["logprior"].float()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().cpu().numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -270,11 +291,20 @@ def main() -> int:
                          "default selection (the faster of RCCL and the hand-written peer-mapped "
                          "kernel if it is exact, probed on the job's GPUs at the first such all-reduce)")
     ap.add_argument("--probe-allreduce", action="store_true",
-                    help="run the all-reduce probe on any device (it runs by default on >1 GPU)")
+                    help="with --full: run the all-reduce probe on any device (on >1 GPU it runs anyway)")
     ap.add_argument("--ingest-rows", type=int, default=-1,
-                    help="rows per rank of the ingest-inclusive CSV measurement (0 = skip; default 2^26 "
-                         "on a single GPU, 2^24 per rank on more)")
+                    help="with --full: rows per rank of the ingest-inclusive CSV measurement (0 = skip; "
+                         "default 2^26 on a single GPU, 2^24 per rank on more)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the extras: the code-columns layout, the "
+                         "ingest-inclusive CSV job and, on more than one GPU, the all-reduce probe and "
+                         "the collective self-test (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the model of the last timed step (counts, class counts, log-probability "
+                         "tables) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
@@ -348,7 +378,11 @@ def main() -> int:
     ms = dt * 1000.0 / args.steps
     rows_per_s = n * comm.world * args.steps / dt
     extra = {"layout": args.layout, "ms_per_step": ms, "count_allreduce": allreduce_choice, "hbm_gbps_per_gpu": n * bytes_per_row / (ms / 1000.0) / 1e9}
-    if args.layout == "rowpacked" and table.rowpack is not None:
+    if args.dump_outputs and comm.rank == 0:
+        _dump_outputs(nb, args.dump_outputs)      # before the extras below fit the model again
+    # the extras of --full: measurements next to the headline, in runs of their own after the timed
+    # steps (a plain run goes straight to the result line)
+    if args.full and args.layout == "rowpacked" and table.rowpack is not None:
         rp, table.rowpack = table.rowpack, None
         k = max(1, min(args.steps, 5))
         step()
@@ -356,7 +390,7 @@ def main() -> int:
         extra["columns_rows_per_s_per_gpu"] = n * k / t1
         extra["columns_hbm_gbps_per_gpu"] = n * (codes.shape[0] + 1) * k / t1 / 1e9
         table.rowpack = rp
-    if comm.world > 1 and (dev.type == "cuda" or args.probe_allreduce):
+    if args.full and comm.world > 1 and (dev.type == "cuda" or args.probe_allreduce):
         try:
             extra["rccl_all_reduce"] = _allreduce_probe(comm, dev)
         except Exception as e:      # a probe failure must not lose the measured headline
@@ -369,7 +403,7 @@ def main() -> int:
     # every rank ingests its own file (2^26 records on one GPU; 2^24 per rank on more, so 8 ranks'
     # files fit /dev/shm together); the job's rate is the sum of records over the SLOWEST rank's time
     ingest_rows = args.ingest_rows if args.ingest_rows >= 0 else ((1 << 26) if comm.world == 1 else (1 << 24))
-    if ingest_rows > 0 and (dev.type == "cuda" or args.ingest_rows > 0):
+    if args.full and ingest_rows > 0 and (dev.type == "cuda" or args.ingest_rows > 0):
         try:
             comm.barrier()
             ing = _ingest(ingest_rows, schema, dev, comm)

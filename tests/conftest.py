@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REF = "/root/reference"
+FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures")
 
 
 def pytest_configure(config):
@@ -17,15 +17,11 @@ def pytest_configure(config):
 
 @pytest.fixture
 def ref_resource():
+    """Path of one of the reference's small configs / schemas, vendored under tests/fixtures."""
     def _p(name):
-        p = os.path.join(REF, "resource", name)
-        if os.path.exists(p):
-            return p
-        # vendored copies of the small reference configs / schemas (GPU boxes have no reference)
-        v = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", name)
-        if os.path.exists(v):
-            return v
-        pytest.skip(f"reference resource {name} not mounted")
+        v = os.path.join(FIXTURES, name)
+        assert os.path.exists(v), f"tests/fixtures/{name} is missing"
+        return v
     return _p
 
 

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests._dist import free_port
@@ -26,18 +27,29 @@ def _run(cmd, timeout=600):
     return json.loads(lines[0])
 
 
-def test_bench_single_rank_contract():
-    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--ingest-rows", "0"])
+def test_bench_single_rank_contract(tmp_path):
+    out = tmp_path / "dump"
+    d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--ingest-rows", "0",
+              "--dump-outputs", str(out)])
     assert KEYS <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["value"] > 0 and d["config"]["parallelism"] == "dp1"
+    # a plain run measures the headline only: the extras belong to --full
+    assert not {"columns_rows_per_s_per_gpu", "ingest", "rccl_all_reduce", "comm_selftest"} & set(d["extra"])
+    # --dump-outputs: the model of the last timed step, float32 / float64, every record counted once
+    arrs = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(arrs) == {"counts", "class_n", "logp", "logfp", "logprior"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    n = d["config"]["rows_per_gpu"]
+    assert arrs["class_n"].sum() == n and arrs["counts"].sum() == 5 * n
+    assert arrs["logp"].shape == arrs["counts"].shape and np.isfinite(arrs["logp"]).all()
 
 
 def test_bench_two_ranks_selftest():
     port = free_port()
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
               "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-              "--steps", "2", "--warmup", "1", "--probe-allreduce", "--ingest-rows", "0"])
+              "--steps", "2", "--warmup", "1", "--full", "--probe-allreduce", "--ingest-rows", "0"])
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["config"]["global_batch"] == 2 * d["config"]["rows_per_gpu"]
     st = d["extra"]["comm_selftest"]

@@ -27,7 +27,7 @@ def _dev(cols, n, delim, tmp, like):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("delim", [",", "::"])
+@pytest.mark.parametrize("delim", [",", pytest.param("::", id="dcolon")])   # "::" separates node ids
 def test_device_formatter_equals_host(cuda, tmp_path, delim):
     g = torch.Generator().manual_seed(0)
     n = 5000
