@@ -200,6 +200,72 @@ void class_histogram_dense(const at::Tensor& dense, int64_t n, int64_t B, std::v
                              reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()), cur_stream(dense));
 }
 
+// Mixed-radix record streams.  Every layout argument is a host list: nothing here reads a device
+// tensor back (that would be a blocking copy draining the stream on every training step).
+static std::vector<int> radix_ints(const std::vector<int64_t>& v, int64_t F, const char* what) {
+  TORCH_CHECK((int64_t)v.size() == F, what, ": F entries");
+  std::vector<int> r(F);
+  for (int64_t k = 0; k < F; ++k) {
+    TORCH_CHECK(v[k] >= 0 && v[k] < (int64_t(1) << 30), what, " out of range");
+    r[k] = (int)v[k];
+  }
+  return r;
+}
+
+// (J, B, R) of a mixed-radix layout: joint states, bits per record, replicas of the joint table
+std::vector<int64_t> radix_shape(std::vector<int64_t> radices, int64_t class_radix, int64_t n_classes,
+                                 int64_t total_bins) {
+  TORCH_CHECK(class_radix >= 1 && class_radix <= 3 && n_classes >= 1 && n_classes <= 2 && total_bins >= 0 &&
+                  total_bins < (int64_t(1) << 24), "bad class radix / classes / table width");
+  int64_t J = class_radix;
+  for (int64_t r : radices) {
+    TORCH_CHECK(r >= 1 && r <= 9, "radix out of range");
+    J *= r;
+    TORCH_CHECK(J <= (int64_t(1) << 40), "too many joint states");
+  }
+  return {J, (int64_t)avk::radix_bits(J), (int64_t)avk::radix_replicas(J, (int)n_classes, (int)total_bins)};
+}
+
+at::Tensor pack_radix(const at::Tensor& words, int64_t n, int64_t B, std::vector<int64_t> shifts,
+                      std::vector<int64_t> widths, std::vector<int64_t> radices, std::vector<int64_t> bins_host,
+                      int64_t label_shift, int64_t class_radix, int64_t n_classes) {
+  CHECK_DEV(words);
+  CHECK_DTYPE(words, at::kShort);
+  TORCH_CHECK(words.dim() == 1 && n >= 0 && n <= words.numel(), "words must be [>= n]");
+  TORCH_CHECK(B >= 4 && B <= 15, "4..15 bits per record");
+  const int64_t F = (int64_t)shifts.size();
+  TORCH_CHECK(F >= 1 && F <= 8, "1..8 packed fields");
+  const auto sh = radix_ints(shifts, F, "shifts"), wd = radix_ints(widths, F, "widths");
+  const auto rad = radix_ints(radices, F, "radices"), hb = radix_ints(bins_host, F, "bins");
+  auto dense = at::zeros({std::max<int64_t>(1, avk::dense_words(n, (int)B))}, words.options().dtype(at::kInt));
+  DevGuard g(words.device());
+  avk::pack_radix(reinterpret_cast<const uint16_t*>(words.data_ptr()), n, (int)B, sh.data(), wd.data(), rad.data(),
+                  hb.data(), (int)F, (int)label_shift, (int)class_radix, (int)n_classes,
+                  reinterpret_cast<uint32_t*>(dense.data_ptr<int>()), cur_stream(words));
+  return dense;
+}
+
+void class_histogram_radix(const at::Tensor& dense, int64_t n, int64_t B, std::vector<int64_t> radices,
+                           std::vector<int64_t> bins_host, std::vector<int64_t> offs_host, int64_t class_radix,
+                           int64_t total_bins, int64_t n_classes, at::Tensor& out, bool count_labels) {
+  CHECK_DEV(dense);
+  CHECK_DTYPE(dense, at::kInt);
+  TORCH_CHECK(B >= 4 && B <= 15 && n >= 0 && dense.numel() >= avk::dense_words(n, (int)B), "radix stream too short");
+  const int64_t F = (int64_t)radices.size();
+  TORCH_CHECK(F >= 1 && F <= 8, "1..8 packed fields");
+  const auto rad = radix_ints(radices, F, "radices"), hb = radix_ints(bins_host, F, "bins");
+  const auto ho = radix_ints(offs_host, F, "offs");
+  TORCH_CHECK(n_classes >= 1 && n_classes <= 2, "1 or 2 classes");
+  TORCH_CHECK(total_bins >= 1 && total_bins < (int64_t(1) << 24), "bad table width");
+  CHECK_DEV(out); CHECK_DTYPE(out, at::kLong);
+  TORCH_CHECK(out.numel() == n_classes * total_bins, "out must be [C * TB]");
+  DevGuard g(dense.device());
+  avk::class_histogram_radix(reinterpret_cast<const uint32_t*>(dense.data_ptr<int>()), n, (int)B, rad.data(), hb.data(),
+                             ho.data(), (int)F, (int)class_radix, (int)total_bins, (int)n_classes,
+                             count_labels ? 1 : 0, reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()),
+                             cur_stream(dense));
+}
+
 void pair_histogram(const at::Tensor& codes, int64_t n, const c10::optional<at::Tensor>& labels,
                     const at::Tensor& bins, const at::Tensor& pairs, const at::Tensor& poff,
                     int64_t max_tab, int64_t n_classes, at::Tensor& out) {
@@ -4041,6 +4107,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("class_histogram_rowpacked", &class_histogram_rowpacked);
   m.def("pack_dense", &pack_dense);
   m.def("class_histogram_dense", &class_histogram_dense);
+  m.def("radix_shape", &radix_shape);
+  m.def("pack_radix", &pack_radix);
+  m.def("class_histogram_radix", &class_histogram_radix);
   m.def("bigram_histogram", &bigram_histogram);
   m.def("class_moments", &class_moments);
   m.def("nb_predict", &nb_predict);

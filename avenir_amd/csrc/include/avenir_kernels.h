@@ -307,6 +307,16 @@ void class_histogram_dense(const uint32_t* dense, long long n, int B, const int*
                            int nfeat, int label_shift, int label_width, const int* d_bins, const int* d_offs,
                            int total_bins, int n_classes, int count_labels, unsigned long long* out,
                            hipStream_t stream);
+// mixed-radix record streams (histogram.hip): code = c + Rc * (f0 + r0 * (f1 + ...)), B = ceil(log2 J)
+// bits per record in the pack_dense container; all arrays are host arrays of nfeat entries
+int radix_bits(long long J);
+int radix_replicas(long long J, int n_classes, int total_bins);
+void pack_radix(const uint16_t* words, long long n, int B, const int* h_shift, const int* h_width, const int* h_radix,
+                const int* h_bins, int nfeat, int label_shift, int class_radix, int n_classes, uint32_t* dense,
+                hipStream_t stream);
+void class_histogram_radix(const uint32_t* dense, long long n, int B, const int* h_radix, const int* h_bins,
+                           const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
+                           int count_labels, unsigned long long* out, hipStream_t stream);
 // K1 device CSV parse (csv.hip)
 long long csv_chunks(long long size);
 // tokens parsed since the last call whose rounding the device could not settle (then re-parse on the

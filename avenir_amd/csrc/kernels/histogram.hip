@@ -9,10 +9,11 @@
 //     J/explore/CramerCorrelation.java:162-182).
 // K4  Markov bigram histogram  out[c][s][s']  (J/markov/MarkovStateTransitionModel.java:116-133).
 //
-// Row-packed records (all codes + one-hot class of a record in <= 15 bits): hist_joint_dense_kernel
-// counts each record with ONE LDS atomic into the block's joint table (dense B-bit record stream,
-// 1.63 B/record for churn) and takes the class-conditional marginals once per block — the NB
-// training headline; hist_joint_kernel / hist_rowpack_kernel are the 16-bit-word variants.
+// Row-packed records (all codes + class of a record in <= 15 bits): hist_joint_radix_kernel counts
+// each record with ONE LDS atomic into the block's joint table (dense stream of mixed-radix codes,
+// 11 bits = 1.375 B/record for churn, the code being the table cell) and takes the class-conditional
+// marginals once per block — the NB training headline; hist_joint_dense_kernel streams the same
+// records as bit fields (13 bits for churn), hist_joint_kernel / hist_rowpack_kernel the 16-bit words.
 //
 // Data layout (SoA, feature-major): codes are uint8 [F][ld] with ld % 16 == 0, so every lane
 // streams 16 rows per 128-bit load.  A code is either < bins[f] or the missing sentinel 255.
@@ -769,6 +770,142 @@ __global__ __launch_bounds__(HB) void pack_dense_kernel(const uint16_t* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Mixed-radix records: the bit-field record spends a whole number of bits per field (churn: 13 bits
+// for 4*3*3*3*5*2 = 1080 states); the mixed-radix code  c + Rc * (f0 + r0 * (f1 + r1 * ...))  of the
+// same record needs ceil(log2 J) bits (churn: 11) and IS the joint-table cell index, so the table has
+// J cells instead of 2^bits and no slot map is needed.  The smaller table leaves room for up to 32
+// interleaved replicas (cell * R + lane % R): with R = 32 every lane of a 32-lane LDS group owns its
+// own bank and random records cannot conflict.
+// ---------------------------------------------------------------------------------------------
+struct RadixSpec {
+  int rad[8];   // radix of feature k: bins[k], or bins[k] + 1 when the data holds its missing code
+  int bins[8];  // digits >= bins[k] (the missing digit) are not counted
+  int offs[8];  // first output column of feature k
+  int crad;     // class radix: 1 = no class digit (C = 1), 2, or 3 when unknown labels occur (digit 2)
+};
+
+// 16-bit words of pack_rows -> dense B-bit stream of mixed-radix codes (container as pack_dense).
+// Every digit is clamped to its radix, so a code is < J whatever the words hold.
+__global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restrict__ words, long long n, int B,
+                                                        RowPackSpec spec, RadixSpec rs, int nfeat,
+                                                        uint32_t* __restrict__ dense) {
+  const long long groups = (n + 31) >> 5;
+  const long long stride = (long long)gridDim.x * HB;
+  for (long long g = (long long)blockIdx.x * HB + threadIdx.x; g < groups; g += stride) {
+    uint32_t d[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) d[i] = 0;
+    for (int k = 0; k < 32; ++k) {
+      const long long r = (g << 5) + k;
+      uint32_t v = 0;
+      if (r < n) {
+        const uint32_t w = words[r];
+        uint32_t mult = 1;
+        if (rs.crad > 1) {
+          const uint32_t lb = __builtin_amdgcn_ubfe(w, (unsigned)spec.lsh, 2u);
+          const uint32_t cd = lb == 1u ? 0u : (lb == 2u ? 1u : 2u);
+          v = min(cd, (uint32_t)rs.crad - 1u);
+          mult = (uint32_t)rs.crad;
+        }
+        for (int f = 0; f < nfeat; ++f) {
+          const uint32_t code = __builtin_amdgcn_ubfe(w, (unsigned)spec.sh[f], (unsigned)spec.w[f]);
+          v += min(code, (uint32_t)rs.rad[f] - 1u) * mult;
+          mult *= (uint32_t)rs.rad[f];
+        }
+      }
+      const int bit = k * B, i = bit >> 5, sh = bit & 31;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {  // register-indexed writes unrolled (no scratch)
+        if (q == i) d[q] |= v << sh;
+        if (q == i + 1 && sh + B > 32) d[q] |= v >> (32 - sh);
+      }
+    }
+    for (int i = 0; i < B; ++i) dense[g * B + i] = d[i];
+  }
+}
+
+// One LDS atomic per record into s_joint[(code << log2 R) + lane % R]; the hot loop is
+// hist_joint_dense_kernel's (B dword loads per lane, 32 extractions at compile-time offsets) with a
+// single shift-add as the cell address.  Epilogue: S = min(R, 8) lanes share a cell's R replicas
+// (item i = cell * S + part reads replica (i + S q) % R in round q: for R = 32 a 32-lane group
+// touches 32 different banks; with S = 1 this is the rotation (cell + q) % R), a cell's parts are
+// summed across its S lanes, the cell index is decoded digit by digit and added into the [C][TB]
+// table, and that table is flushed with one global atomic per non-zero entry.
+template <int B>
+__global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* __restrict__ dense, long long n,
+                                                                RadixSpec rs, int J, int log2r, int nfeat,
+                                                                int n_classes, int total_bins, int count_labels,
+                                                                unsigned long long* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int s_joint[];
+  constexpr unsigned M = (1u << B) - 1u;
+  const int NT = (int)blockDim.x;
+  const int R = 1 << log2r;
+  unsigned int* s_small = s_joint + ((size_t)J << log2r);
+  for (int i = threadIdx.x; i < (J << log2r) + n_classes * total_bins; i += NT) s_joint[i] = 0;
+  // byte address of a record's counter = lane base + (code << (log2 R + 2)): one v_lshl_add_u32
+  char* const my = reinterpret_cast<char*>(s_joint + (threadIdx.x & (unsigned)(R - 1)));
+  const unsigned lr = (unsigned)log2r + 2u;
+  __syncthreads();
+  const long long groups = (n + 31) >> 5;
+  const long long stride = (long long)gridDim.x * NT;
+  for (long long g = (long long)blockIdx.x * NT + threadIdx.x; g < groups; g += stride) {
+    uint32_t d[B + 1];
+    const uint32_t* src = dense + g * B;
+#pragma unroll
+    for (int i = 0; i < B; ++i) d[i] = src[i];
+    d[B] = 0;
+    const long long left = n - (g << 5);
+    auto rec = [&](int k) __attribute__((always_inline)) -> unsigned {
+      const int bit = k * B, i = bit >> 5, sh = bit & 31;
+      if (sh + B <= 32) return __builtin_amdgcn_ubfe(d[i], (unsigned)sh, (unsigned)B);
+      return __builtin_amdgcn_alignbit(d[i + 1], d[i], (unsigned)sh) & M;
+    };
+    if (left >= 32) {  // every group but the last: no per-record predicate
+#pragma unroll
+      for (int k = 0; k < 32; ++k) atomicAdd(reinterpret_cast<unsigned int*>(my + (rec(k) << lr)), 1u);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k)
+        if (k < left) atomicAdd(reinterpret_cast<unsigned int*>(my + (rec(k) << lr)), 1u);
+    }
+  }
+  __syncthreads();
+  const int ls = log2r < 3 ? log2r : 3;  // S = 2^ls lanes per cell
+  const int S = 1 << ls;
+  const int items = J << ls;
+  for (int base = 0; base < items; base += NT) {  // block-uniform bound: every lane takes part in the shuffles
+    const int i = base + (int)threadIdx.x;
+    const int cell = i >> ls;
+    unsigned cnt = 0;
+    if (i < items)
+      for (int q = 0; q < (R >> ls); ++q) cnt += s_joint[((size_t)cell << log2r) + ((i + (q << ls)) & (R - 1))];
+    for (int o = S >> 1; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+    unsigned j = (unsigned)cell;
+    int c = 0;
+    if (rs.crad > 1) {
+      c = (int)(j % (unsigned)rs.crad);
+      j /= (unsigned)rs.crad;
+    }
+    // the first lane of a cell holds its count; an unknown class is not counted (as in the column histogram)
+    if (i < items && !(i & (S - 1)) && cnt && c < n_classes) {
+      unsigned int* row = s_small + c * total_bins;
+      for (int kf = 0; kf < nfeat; ++kf) {
+        const unsigned rk = (unsigned)rs.rad[kf];
+        const int code = (int)(j % rk);
+        j /= rk;
+        if (code < rs.bins[kf]) atomicAdd(&row[rs.offs[kf] + code], cnt);
+      }
+      if (count_labels) atomicAdd(&row[total_bins - 1], cnt);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_classes * total_bins; i += NT) {
+    const unsigned cnt = s_small[i];
+    if (cnt) atomicAdd(&out[i], (unsigned long long)cnt);
+  }
+}
+
 int hist_joint_lds(int nbits, int n_classes, int total_bins) {
   return (int)(sizeof(unsigned) * ((size_t(1) << nbits) + (size_t)n_classes * total_bins));
 }
@@ -1217,6 +1354,121 @@ void class_histogram_dense(const uint32_t* dense, long long n, int B, const int*
     AV_DENSE(12) AV_DENSE(13) AV_DENSE(14) AV_DENSE(15)
 #undef AV_DENSE
     default: throw std::runtime_error("dense histogram: 4..15 bits per record");
+  }
+}
+
+// ---- mixed-radix records ----
+constexpr int kLdsPerCu = 160 * 1024;
+
+// J = product of the radices; throws on anything the kernels could not index safely
+static RadixSpec radix_spec(const int* h_radix, const int* h_bins, const int* h_offs, int nfeat, int class_radix,
+                            int n_classes, int total_bins, long long* J) {
+  if (nfeat < 1 || nfeat > 8 || n_classes < 1 || n_classes > 2)
+    throw std::runtime_error("radix histogram: 1 <= F <= 8, C <= 2");
+  if (n_classes == 1 ? class_radix != 1 : (class_radix != 2 && class_radix != 3))
+    throw std::runtime_error("radix histogram: class radix 1 (C = 1), 2 or 3 (C = 2)");
+  RadixSpec rs{};
+  rs.crad = class_radix;
+  long long j = class_radix;
+  for (int k = 0; k < nfeat; ++k) {
+    if (h_bins[k] < 1 || (h_radix[k] != h_bins[k] && h_radix[k] != h_bins[k] + 1))
+      throw std::runtime_error("radix histogram: a radix is bins or bins + 1");
+    if (h_offs[k] < 0 || h_offs[k] + h_bins[k] > total_bins)
+      throw std::runtime_error("radix histogram: feature bins outside the table");
+    rs.rad[k] = h_radix[k];
+    rs.bins[k] = h_bins[k];
+    rs.offs[k] = h_offs[k];
+    j *= h_radix[k];
+    if (j > (1LL << 15)) throw std::runtime_error("radix histogram: more than 2^15 joint states");
+  }
+  *J = j;
+  return rs;
+}
+
+int radix_bits(long long J) {
+  int b = 0;
+  while ((1LL << b) < J) ++b;
+  return b;
+}
+
+void pack_radix(const uint16_t* words, long long n, int B, const int* h_shift, const int* h_width, const int* h_radix,
+                const int* h_bins, int nfeat, int label_shift, int class_radix, int n_classes, uint32_t* dense,
+                hipStream_t stream) {
+  if (n <= 0) return;
+  const int offs0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long J = 0;
+  const RadixSpec rs = radix_spec(h_radix, h_bins, offs0, nfeat, class_radix, n_classes, 1 << 30, &J);
+  if (B < 4 || B > 15 || radix_bits(J) != B) throw std::runtime_error("pack_radix: B = ceil(log2 J) in 4..15");
+  RowPackSpec spec{};
+  for (int k = 0; k < nfeat; ++k) {
+    if (h_width[k] < 1 || h_width[k] > 3 || h_shift[k] < 0 || h_shift[k] + h_width[k] > 16)
+      throw std::runtime_error("pack_radix: fields of 1..3 bits inside the 16-bit word");
+    spec.sh[k] = h_shift[k];
+    spec.w[k] = h_width[k];
+  }
+  if (n_classes > 1 && (label_shift < 0 || label_shift + 2 > 16))
+    throw std::runtime_error("pack_radix: the class is two one-hot bits inside the 16-bit word");
+  spec.lsh = n_classes > 1 ? label_shift : 0;
+  pack_radix_kernel<<<av::stream_grid((n + 31) >> 5, HB, 1, 4096), HB, 0, stream>>>(words, n, B, spec, rs, nfeat, dense);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+// replicas of the J-cell table: the largest power of two <= 32 (<= AVMI_JOINT_REPLICAS when set)
+// with 4 (J R + C TB) bytes inside the CU's LDS
+int radix_replicas(long long J, int n_classes, int total_bins) {
+  int want = 32;
+  if (const char* e = std::getenv("AVMI_JOINT_REPLICAS")) want = std::max(1, std::min(32, std::atoi(e)));
+  int R = 1;
+  while (R * 2 <= want && 4LL * (J * (R * 2) + (long long)n_classes * total_bins) <= kLdsPerCu) R *= 2;
+  return R;
+}
+
+template <int B>
+static void launch_joint_radix(const uint32_t* dense, long long n, const RadixSpec& rs, int J, int nfeat,
+                               int n_classes, int total_bins, int count_labels, unsigned long long* out,
+                               hipStream_t stream) {
+  const int R = radix_replicas(J, n_classes, total_bins);
+  const long long lds = 4LL * ((long long)J * R + (long long)n_classes * total_bins);
+  if (lds > kLdsPerCu) throw std::runtime_error("radix histogram: joint table exceeds LDS");
+  int log2r = 0;
+  while ((1 << log2r) < R) ++log2r;
+  // threads per block: at least 16 waves per CU next to the tables that fit it
+  const int per_cu = (int)(kLdsPerCu / lds);
+  const int NT = per_cu >= 4 ? HB : (per_cu >= 2 ? 512 : 1024);
+  auto kern = hist_joint_radix_kernel<B>;
+  // occupancy query and LDS opt-in once per (device, configuration), not per training step
+  static int c_dev = -1, c_lds = -1, c_nt = 0, c_res = 0;
+  int dev = 0;
+  AV_HIP_CHECK(hipGetDevice(&dev));
+  if (c_dev != dev || c_lds != (int)lds || c_nt != NT) {
+    if (lds > 64 * 1024)
+      AV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+    c_res = av::resident_blocks((const void*)kern, NT, (size_t)lds);
+    c_dev = dev;
+    c_lds = (int)lds;
+    c_nt = NT;
+  }
+  const int grid = std::max(1, std::min(av::stream_grid(std::max(1LL, (n + 31) >> 5), NT, 1, 8192), c_res));
+  kern<<<grid, NT, (size_t)lds, stream>>>(dense, n, rs, J, log2r, nfeat, n_classes, total_bins, count_labels, out);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+void class_histogram_radix(const uint32_t* dense, long long n, int B, const int* h_radix, const int* h_bins,
+                           const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
+                           int count_labels, unsigned long long* out, hipStream_t stream) {
+  if (n <= 0) return;
+  long long J = 0;
+  const RadixSpec rs = radix_spec(h_radix, h_bins, h_offs, nfeat, class_radix, n_classes, total_bins, &J);
+  if (radix_bits(J) != B) throw std::runtime_error("radix histogram: B = ceil(log2 J)");
+  if (count_labels && total_bins < 1) throw std::runtime_error("radix histogram: no class-count column");
+  switch (B) {
+#define AV_RADIX(BB) \
+  case BB: launch_joint_radix<BB>(dense, n, rs, (int)J, nfeat, n_classes, total_bins, count_labels, out, stream); break;
+    AV_RADIX(4) AV_RADIX(5) AV_RADIX(6) AV_RADIX(7) AV_RADIX(8) AV_RADIX(9) AV_RADIX(10) AV_RADIX(11)
+    AV_RADIX(12) AV_RADIX(13) AV_RADIX(14) AV_RADIX(15)
+#undef AV_RADIX
+    default: throw std::runtime_error("radix histogram: 4..15 bits per record");
   }
 }
 

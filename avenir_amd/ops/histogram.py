@@ -88,15 +88,66 @@ class RowPacked:
     label_shift: int
     label_width: int         # 0: no class field (C = 1)
     n_classes: int
-    dense: torch.Tensor | None = None   # GPU: the same records as a dense B-bit stream (pack_dense)
-    bits: int = 16                      # B: bits per record actually used
+    dense: torch.Tensor | None = None   # GPU: the same records as a dense B-bit stream (see ensure_dense)
+    bits: int = 16                      # B: bits per record of ``dense`` (of the word's fields without one)
+    radices: list[int] | None = None    # mixed-radix digits of the features (``radix_layout``)
+    class_radix: int = 1                # 1: no class digit (C = 1); 2; 3: digit 2 = unknown class
+    dense_is_radix: bool = False        # ``dense`` holds mixed-radix codes, not the bit-field records
+    field_bits: int | None = None       # bits of the bit-field record when ``bits`` counts the radix code
+    bitfield: torch.Tensor | None = None  # the bit-field stream next to a radix ``dense`` (built on first use)
 
     def ensure_dense(self) -> "RowPacked":
-        """Attach the dense B-bit stream (32 records per B dwords, 1.6 B/record for churn) the
-        joint-table kernel streams instead of the 16-bit words; GPU only, B in 4..15."""
-        if self.dense is None and self.words.is_cuda and 4 <= self.bits <= 15 and self.n > 0:
+        """Attach the dense B-bit stream (32 records per B dwords) the joint-table kernels stream
+        instead of the 16-bit words; GPU only, B in 4..15.  With ``radices`` set and
+        ceil(log2 J) in 4..15 the records are mixed-radix codes (churn: 11 bits, 1.375 B/record),
+        else the word's bit fields back to back (churn: 13 bits)."""
+        if self.dense is not None or not self.words.is_cuda or self.n <= 0:
+            return self
+        if self.radices is not None:
+            tb = sum(self.bins) + 1
+            _, B, _ = _native.C().radix_shape(list(self.radices), int(self.class_radix), int(self.n_classes), tb)
+            if 4 <= B <= 15:
+                self.dense = _native.C().pack_radix(self.words, int(self.n), int(B), list(self.shifts),
+                                                    list(self.widths), list(self.radices), list(self.bins),
+                                                    int(self.label_shift), int(self.class_radix),
+                                                    int(self.n_classes))
+                self.field_bits, self.bits, self.dense_is_radix = self.bits, int(B), True
+                return self
+        if 4 <= self.bits <= 15:
             self.dense = _native.C().pack_dense(self.words, int(self.n), int(self.bits))
         return self
+
+    def ensure_bitfield(self) -> torch.Tensor | None:
+        """The bit-field stream of the records (AVMI_ROWPACK_KERNEL=bitfield): ``dense`` itself
+        unless that holds mixed-radix codes; then packed from the words on first use."""
+        if not self.dense_is_radix:
+            return self.dense
+        if self.bitfield is None and 4 <= self.field_bits <= 15:
+            self.bitfield = _native.C().pack_dense(self.words, int(self.n), int(self.field_bits))
+        return self.bitfield
+
+
+def radix_layout(bins: Sequence[int], n_classes: int, missing: Sequence[bool] | None = None,
+                 unknown: bool = True, count_labels: bool = True):
+    """Mixed-radix code of a record, class digit least significant, then feature 0, 1, ...:
+    feature k's digit is its code, of radix bins[k], or bins[k] + 1 with the missing code as digit
+    bins[k] when ``missing[k]``; the class digit (C = 2 only) is the class, of radix 2, or 3 with
+    digit 2 for an unknown class when ``unknown``.  Returns (radices, class_radix, J, B, R): the
+    joint states, B = ceil(log2 J) bits per record and the replicas of the J-cell table the kernel
+    keeps in LDS next to the [C, sum(bins) (+1)] table; None when B is outside 4..15 (no stream)."""
+    bins = [int(b) for b in bins]
+    C = int(n_classes)
+    if missing is None:
+        missing = [True] * len(bins)
+    if not bins or len(bins) > 8 or C < 1 or C > 2 or min(bins) < 1 or max(bins) > 8:
+        return None
+    radices = [b + 1 if m else b for b, m in zip(bins, missing)]
+    class_radix = 1 if C == 1 else (3 if unknown else 2)
+    tb = sum(bins) + (1 if count_labels else 0)
+    J, B, R = _native.C().radix_shape(radices, class_radix, C, tb)
+    if not 4 <= B <= 15:
+        return None
+    return radices, class_radix, int(J), int(B), int(R)
 
 
 def rowpack_layout(bins: Sequence[int], n_classes: int, missing: Sequence[bool] | None = None):
@@ -151,7 +202,11 @@ def pack_rows(codes: torch.Tensor, n: int, bins: Sequence[int], labels: torch.Te
         body |= torch.where(v < C, 1 << v.clamp_max(C - 1), torch.zeros_like(v)) << lsh
     words = torch.where(w >= 32768, w - 65536, w).to(torch.int16)
     bits = max([s + wd for s, wd in zip(shifts, widths)] + [lsh + lw])
-    return RowPacked(words, int(n), bins, shifts, widths, lsh, lw, C, bits=bits).ensure_dense()
+    # mixed-radix digits (radix_layout): a missing / unknown digit only where the data holds one
+    unknown = bool((labels[:n] >= C).any()) if lw and n else False
+    radices = [b + 1 if m else b for b, m in zip(bins, missing)]
+    return RowPacked(words, int(n), bins, shifts, widths, lsh, lw, C, bits=bits, radices=radices,
+                     class_radix=1 if C == 1 else (3 if unknown else 2)).ensure_dense()
 
 
 def unpack_rows(rp: RowPacked) -> tuple[torch.Tensor, torch.Tensor | None]:
@@ -178,8 +233,10 @@ def unpack_rows(rp: RowPacked) -> tuple[torch.Tensor, torch.Tensor | None]:
 def class_histogram_packed(rp: RowPacked, out: torch.Tensor | None = None,
                            count_labels: bool = False) -> torch.Tensor:
     """``class_histogram`` over row-packed records (same ``[C, sum(bins) (+1)]`` int64 result).
-    GPU: the K2 row-packed kernel streams 2 bytes per record (8 records per 16-byte load)
-    instead of F + 1 bytes of code columns; CPU: unpack + the column reference."""
+    GPU: the K2 joint-table kernel streams the records' dense stream (``ensure_dense``: mixed-radix
+    codes, else bit fields), or the 16-bit words, instead of F + 1 bytes of code columns;
+    AVMI_ROWPACK_KERNEL=bitfield / joint / nibble select the bit-field stream and the two word
+    kernels.  CPU: unpack + the column reference."""
     C = rp.n_classes
     tb = sum(rp.bins) + (1 if count_labels else 0)
     if out is None:
@@ -195,9 +252,16 @@ def class_histogram_packed(rp: RowPacked, out: torch.Tensor | None = None,
         order = sorted(range(len(rp.bins)), key=lambda k: (C == 2 and rp.widths[k] > 2, k))
         dev = rp.words.device
         kind = os.environ.get("AVMI_ROWPACK_KERNEL", "dense")
-        if kind == "dense" and rp.dense is not None:
-            # dense B-bit records, one LDS atomic per record into the joint table
-            _native.C().class_histogram_dense(rp.dense, int(rp.n), int(rp.bits), list(rp.shifts), list(rp.widths),
+        if kind == "dense" and rp.dense_is_radix:
+            # mixed-radix records: the code is the cell of the J-cell joint table, one LDS atomic per record
+            _native.C().class_histogram_radix(rp.dense, int(rp.n), int(rp.bits), list(rp.radices), list(rp.bins),
+                                              offs, int(rp.class_radix), tb, C, out, bool(count_labels))
+            return out
+        stream = rp.ensure_bitfield() if kind in ("dense", "bitfield") else None
+        if stream is not None:
+            # bit-field records back to back, one LDS atomic per record into the 2^bits joint table
+            fb = rp.field_bits if rp.dense_is_radix else rp.bits
+            _native.C().class_histogram_dense(stream, int(rp.n), int(fb), list(rp.shifts), list(rp.widths),
                                               rp.label_shift, rp.label_width, _dev_i32(rp.bins, dev),
                                               _dev_i32(offs, dev), tb, C, out, bool(count_labels),
                                               list(rp.bins), offs)
