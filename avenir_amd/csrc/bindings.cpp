@@ -1453,6 +1453,115 @@ void ga_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict
                  cur_stream(cost));
 }
 
+// island GA over a meeting-schedule domain (optim.hip::ga_meeting_kernel).  The domain tensors are
+// small; they are read back once here so that no index, mask bit or time can take the kernel out of
+// its LDS tables.
+void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,
+                const at::Tensor& share, const at::Tensor& member, const at::Tensor& role_w, const at::Tensor& blocked,
+                const at::Tensor& ordered, double invalid, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& hist,
+                int64_t G, int64_t m, int64_t r, bool purge_first, bool mutate, int64_t seed, int64_t island_base,
+                int64_t gen_base) {
+  for (const at::Tensor* t : {&days, &hours, &minutes, &dur, &share, &member, &blocked, &ordered}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kInt);
+    TORCH_CHECK(t->is_contiguous(), "ga_meeting: domain tensors must be contiguous");
+  }
+  CHECK_DEV(role_w);
+  CHECK_DTYPE(role_w, at::kFloat);
+  TORCH_CHECK(role_w.is_contiguous() && role_w.dim() == 1, "role_w must be contiguous [Q]");
+  TORCH_CHECK(days.dim() == 1 && hours.dim() == 1 && minutes.dim() == 1 && dur.dim() == 1 && share.dim() == 1 &&
+              member.dim() == 1, "days / hours / minutes / dur / share / member must be 1-d");
+  TORCH_CHECK(blocked.dim() == 2 && blocked.size(1) == 3, "blocked must be [nb, 3] (mask, begin, end)");
+  TORCH_CHECK(ordered.dim() == 2 && ordered.size(1) == 2, "ordered must be [no, 2]");
+  const int64_t nd = days.numel(), nh = hours.numel(), nm = minutes.numel(), M = dur.numel(), Q = member.numel();
+  const int64_t nb = blocked.size(0), no = ordered.size(0);
+  TORCH_CHECK(M >= 1 && M <= 32, "ga_meeting: 1 <= M <= 32 meetings");
+  TORCH_CHECK(Q >= 1 && Q <= 256 && role_w.numel() == Q, "ga_meeting: 1 <= Q <= 256 people, role_w [Q]");
+  TORCH_CHECK(share.numel() == M, "share must be [M]");
+  TORCH_CHECK(nd >= 1 && nd <= 32 && nh >= 1 && nh <= 32 && nm >= 1 && nm <= 32, "value tables of 1..32 entries");
+  TORCH_CHECK(nb <= 16 && no <= 16, "at most 16 blocked entries and 16 ordered pairs");
+  TORCH_CHECK(gen_base >= 0 && gen_base + G < (1LL << 40), "generation counter out of range");
+  const int64_t L = 3 * M;
+  CHECK_DEV(pop);
+  CHECK_DTYPE(pop, at::kShort);
+  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == L && pop.is_contiguous(), "pop must be contiguous [islands, P, 3 M]");
+  const int64_t I = pop.size(0), P = pop.size(1);
+  TORCH_CHECK(P >= 2 && P <= 64 && r >= 1 && r <= std::min<int64_t>(P, 32) && m >= 1 && m <= P,
+              "ga_meeting: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
+  TORCH_CHECK(purge_first || P + r <= 64, "ga_meeting: P + r <= 64 when children join the pool");
+  TORCH_CHECK(avk::ga_meeting_lds((int)P, (int)L, (int)r) <= 64 * 1024, "ga_meeting: more than 64 KiB of LDS");
+  CHECK_DEV(pop_cost);
+  CHECK_DTYPE(pop_cost, at::kFloat);
+  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, "pop_cost must be [islands, P]");
+  CHECK_DEV(hist);
+  CHECK_DTYPE(hist, at::kFloat);
+  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, "hist must be [islands, G]");
+  // the domain on the host: mask bits < M, pairs < M, times that stay exact in int32 and fp32
+  const uint32_t mmask = M == 32 ? 0xffffffffu : ((1u << M) - 1u);
+  auto host = [](const at::Tensor& t) { return t.cpu(); };
+  const at::Tensor hd = host(days), hh = host(hours), hm = host(minutes), hdur = host(dur), hs = host(share),
+                   hmem = host(member), hb = host(blocked), ho = host(ordered);
+  const int64_t lim = 1 << 24;
+  int64_t tmax = 0;
+  {
+    int64_t dmax = 0, hmax = 0, mmax = 0, durmax = 0;
+    for (int64_t i = 0; i < nd; ++i) {
+      const int64_t v = hd.data_ptr<int>()[i];
+      TORCH_CHECK(v >= 1 && v < 256, "days must lie in [1, 256)");
+      dmax = std::max(dmax, v);
+    }
+    for (int64_t i = 0; i < nh; ++i) {
+      const int64_t v = hh.data_ptr<int>()[i];
+      TORCH_CHECK(v >= 0 && v < 1024, "hours must lie in [0, 1024)");
+      hmax = std::max(hmax, v);
+    }
+    for (int64_t i = 0; i < nm; ++i) {
+      const int64_t v = hm.data_ptr<int>()[i];
+      TORCH_CHECK(v >= 0 && v < 65536, "minutes must lie in [0, 65536)");
+      mmax = std::max(mmax, v);
+    }
+    for (int64_t i = 0; i < M; ++i) {
+      const int64_t v = hdur.data_ptr<int>()[i];
+      TORCH_CHECK(v >= 0 && v < lim, "durations out of range");
+      durmax = std::max(durmax, v);
+    }
+    tmax = (dmax - 1) * 86400 + hmax * 3600 + mmax * 60 + durmax;
+    TORCH_CHECK(tmax < lim, "meeting times must stay below 2^24 seconds");
+  }
+  for (int64_t i = 0; i < M; ++i) {
+    const uint32_t s = (uint32_t)hs.data_ptr<int>()[i];
+    TORCH_CHECK((s & ~mmask) == 0 && !((s >> i) & 1u), "share: bits < M, no meeting shares with itself");
+    for (int64_t j = 0; j < M; ++j)
+      TORCH_CHECK(((s >> j) & 1u) == (((uint32_t)hs.data_ptr<int>()[j] >> i) & 1u), "share must be symmetric");
+  }
+  for (int64_t q = 0; q < Q; ++q)
+    TORCH_CHECK(((uint32_t)hmem.data_ptr<int>()[q] & ~mmask) == 0, "member: mask bits must be < M");
+  for (int64_t b = 0; b < nb; ++b) {
+    const int* e = hb.data_ptr<int>() + 3 * b;
+    TORCH_CHECK(((uint32_t)e[0] & ~mmask) == 0, "blocked: mask bits must be < M");
+    TORCH_CHECK(e[1] >= 0 && e[1] <= e[2] && e[2] < lim, "blocked: 0 <= begin <= end < 2^24 seconds");
+  }
+  for (int64_t o = 0; o < no; ++o) {
+    const int* e = ho.data_ptr<int>() + 2 * o;
+    TORCH_CHECK(e[0] >= 0 && e[0] < M && e[1] >= 0 && e[1] < M, "ordered: meeting indices must be < M");
+  }
+  if (pop.numel()) {
+    const at::Tensor hi = pop.view({-1, 3}).amax(0).cpu(), lo = pop.min().cpu();
+    const int16_t* h = hi.data_ptr<int16_t>();
+    TORCH_CHECK(lo.item<int16_t>() >= 0 && h[0] < nd && h[1] < nh && h[2] < nm,
+                "solution indices out of range of their value tables");
+  }
+  DevGuard g(pop.device());
+  avk::GaMeetingDomain dom{days.data_ptr<int>(), hours.data_ptr<int>(), minutes.data_ptr<int>(), (int)nd, (int)nh,
+                           (int)nm, dur.data_ptr<int>(), reinterpret_cast<const unsigned*>(share.data_ptr<int>()),
+                           (int)M, reinterpret_cast<const unsigned*>(member.data_ptr<int>()),
+                           role_w.data_ptr<float>(), (int)Q, blocked.data_ptr<int>(), (int)nb,
+                           ordered.data_ptr<int>(), (int)no};
+  avk::ga_meeting(dom, (float)invalid, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(), hist.data_ptr<float>(),
+                  (int)I, (int)P, (int)G, (int)m, (int)r, purge_first ? 1 : 0, mutate ? 1 : 0,
+                  (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(pop));
+}
+
 // ---------------------------------------------------------------------------------------------
 // generalised linear models (K13)
 // ---------------------------------------------------------------------------------------------
@@ -4179,6 +4288,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("sa_assign", &sa_assign);
   m.def("ga_assign", &ga_assign);
   m.def("ga_assign_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_assign_lds((int)P, (int)L, (int)r); });
+  m.def("ga_meeting", &ga_meeting);
+  m.def("ga_meeting_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_meeting_lds((int)P, (int)L, (int)r); });
   m.def("smote_lines", &smote_lines);
   m.def("format_device", &format_device);
   m.def("pairs_within", &pairs_within);

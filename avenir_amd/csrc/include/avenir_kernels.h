@@ -117,6 +117,27 @@ size_t ga_assign_lds(int P, int L, int r);
 void ga_assign(const float* cost, int L, int V, const uint8_t* conflict, float invalid, short* pop, float* pop_cost,
                float* hist, int islands, int P, int G, int m, int r, int purge_first, int mutate, int swap,
                unsigned long long seed, long long island_base, int gen_base, hipStream_t stream);
+// island GA over a meeting-schedule domain: a solution is (day, hour, minute) index triples of M
+// meetings (L = 3 M) into the integer value tables; share / member / blocked masks have one bit per
+// meeting, blocked is [nb][3] (mask, begin s, end s), ordered [no][2] (a before b)
+struct GaMeetingDomain {
+  const int *days, *hours, *minutes;  // [nd], [nh], [nm] value tables
+  int nd, nh, nm;
+  const int* dur;                     // [M] seconds
+  const unsigned* share;              // [M] meetings sharing a participant
+  int M;
+  const unsigned* member;             // [Q] meetings of each person
+  const float* role_w;                // [Q]
+  int Q;
+  const int* blocked;
+  int nb;
+  const int* ordered;
+  int no;
+};
+size_t ga_meeting_lds(int P, int L, int r);
+void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* pop_cost, float* hist, int islands,
+                int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
+                long long island_base, unsigned long long gen_base, hipStream_t stream);
 void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
                short* best_sol, float* best_cost, int P, int iters, float t0, float cool, int interval,
                int geometric, int max_retry, unsigned long long seed, unsigned long long offset,

@@ -143,6 +143,49 @@ __device__ __forceinline__ float ga_price(const short* s, int L, int V, const fl
   return ga_valid(s, L, conflict) ? acc * invL : invalid;
 }
 
+// lane j < n counts the elements ahead of element j by (cost, index) and writes ord[rank] = j
+__device__ __forceinline__ void ga_rank(const float* c, int n, int lane, int* ord) {
+  if (lane < n) {
+    const float cl = c[lane];
+    int rk = 0;
+    for (int j = 0; j < n; ++j) rk += (c[j] < cl) || (c[j] == cl && j < lane);
+    ord[rk] = lane;
+  }
+}
+
+// Step 4 of a generation (both island kernels; every lane of the workgroup calls it): the source
+// of every next-pool slot -> nsrc, then the next pool pb / pc2 gathered from pa / kid.
+__device__ __forceinline__ void ga_replace(const short* pa, short* pb, const short* kid, const float* pc, float* pc2,
+                                           const float* kc, const int* ord, const int* kord, int* nsrc, int P, int L,
+                                           int r, int purge_first, int lane) {
+  if (purge_first) {
+    if (lane < P) nsrc[lane] = lane < P - r ? ord[lane] : P + kord[lane - (P - r)];
+  } else if (lane < P + r) {
+    // candidate lane: member ord-independent index (lane < P) or child kord[lane - P]; its rank
+    // among all candidates by (cost, candidate index)
+    const int src = lane < P ? lane : P + kord[lane - P];
+    const float c = lane < P ? pc[lane] : kc[src - P];
+    int rk = 0;
+    for (int j = 0; j < P + r; ++j) {
+      const int sj = j < P ? j : P + kord[j - P];
+      const float cj = j < P ? pc[j] : kc[sj - P];
+      rk += (cj < c) || (cj == c && j < lane);
+    }
+    if (rk < P) nsrc[rk] = src;
+  }
+  __syncthreads();
+  for (int e = lane; e < P * L; e += 64) {
+    const int slot = e / L, l = e - slot * L;
+    const int src = nsrc[slot];
+    pb[e] = src < P ? pa[(size_t)src * L + l] : kid[(size_t)(src - P) * L + l];
+  }
+  if (lane < P) {
+    const int src = nsrc[lane];
+    pc2[lane] = src < P ? pc[src] : kc[src - P];
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(64) void ga_assign_kernel(
     const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, float invalid,
     short* __restrict__ pop, float* __restrict__ pop_cost, float* __restrict__ hist, int P, int G, int m, int r,
@@ -167,12 +210,7 @@ __global__ __launch_bounds__(64) void ga_assign_kernel(
   __syncthreads();
   for (int g = 0; g < G; ++g) {
     // 1. rank
-    if (lane < P) {
-      const float c = pc[lane];
-      int rk = 0;
-      for (int j = 0; j < P; ++j) rk += (pc[j] < c) || (pc[j] == c && j < lane);
-      ord[rk] = lane;
-    }
+    ga_rank(pc, P, lane, ord);
     __syncthreads();
     if (lane == 0) hist[isl * G + g] = pc[ord[0]];
     // 2. children
@@ -225,40 +263,218 @@ __global__ __launch_bounds__(64) void ga_assign_kernel(
     // 3. price the children
     if (lane < 2 * r) kc[lane] = ga_price(kid + (size_t)lane * L, L, V, cost, conflict, invL, invalid);
     __syncthreads();
+    ga_rank(kc, 2 * r, lane, kord);
+    __syncthreads();
+    // 4. replacement
+    ga_replace(pa, pb, kid, pc, pc2, kc, ord, kord, nsrc, P, L, r, purge_first, lane);
+    short* t = pa; pa = pb; pb = t;
+    float* tc = pc; pc = pc2; pc2 = tc;
+  }
+  for (int e = lane; e < P * L; e += 64) gpop[e] = pa[e];
+  if (lane < P) pop_cost[isl * P + lane] = pc[lane];
+}
+
+// ---- island GA over a meeting-schedule domain (P/app/mesched.py, optimize/domains.py) ----------
+// The frame of ga_assign_kernel (one wave per island, pools / children / costs in LDS for all G
+// generations, Philox by global island index) with the domain's own validity and cost:
+//   * a solution is (day, hour, minute) index triples of M meetings, L = 3 M; meeting i starts at
+//     (days[d] - 1) 86400 + hours[h] 3600 + minutes[mi] 60 s and lasts dur[i] s;
+//   * invalid: two meetings with a common participant overlap, a meeting of a blocked person
+//     overlaps the blocked interval, or an ordered pair (a, b) has end[a] > start[b] — integers only;
+//   * cost: per person q, over the days with a meeting, free = sum(36000 - booked) and
+//     nslots = sum(cnt + 1).  With ndays = the number of distinct days of q's meetings these are
+//     36000 ndays - (total duration of q's meetings) and (meetings of q) + ndays, so no per-day
+//     counters are kept: one OR of day bits per person.  pc = 8 - (free / nslots) / 3600,
+//     cost = sum(pc w) / sum(w) in fp32 with q ascending, multiply and add rounded separately;
+//   * lane c < 2r builds, mutates and prices child c of pair c >> 1 — both lanes of a pair draw the
+//     same Philox word, the crossover cut falls between meetings, mutation moves one index to a
+//     different value of its table (tables of one value are left alone).
+// Each child lane keeps the start second and the day bit of every meeting of its child in two
+// lane-private LDS rows (odd stride: conflict-free), so no private array is indexed dynamically.
+// optimize/ga_meeting.py::ga_meeting_reference is the bit-exact host twin.
+constexpr int MT_MAX_M = 32, MT_MAX_Q = 256, MT_MAX_CARD = 32, MT_MAX_LIST = 16;
+constexpr int MT_DOM_INTS = 3 * MT_MAX_CARD + 2 * MT_MAX_M + 2 * MT_MAX_Q + 5 * MT_MAX_LIST;  // staged domain
+
+__host__ __device__ constexpr size_t mt_a16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+struct MtLds {  // the staged domain
+  const int *days, *hours, *minutes, *dur, *blocked, *ordered;
+  const unsigned *share, *member;
+  const float* role_w;
+  int M, Q, nb, no;
+};
+
+// start second and day bit of meeting i of solution c
+__device__ __forceinline__ void mt_place(const MtLds& D, const short* c, int i, int* st, unsigned* db) {
+  const int d = c[3 * i];
+  st[i] = (D.days[d] - 1) * 86400 + D.hours[c[3 * i + 1]] * 3600 + D.minutes[c[3 * i + 2]] * 60;
+  db[i] = 1u << d;
+}
+
+__device__ __forceinline__ bool mt_valid(const MtLds& D, const int* st) {
+  bool ok = true;
+  for (int i = 1; i < D.M; ++i) {
+    unsigned mk = D.share[i] & ((1u << i) - 1u);  // share is symmetric: pairs j < i
+    const int si = st[i], ei = si + D.dur[i];
+    while (mk) {
+      const int j = __ffs(mk) - 1;
+      mk &= mk - 1;
+      const int sj = st[j];
+      ok &= !(si < sj + D.dur[j] && sj < ei);
+    }
+  }
+  for (int b = 0; b < D.nb; ++b) {
+    unsigned mk = (unsigned)D.blocked[3 * b];
+    const int bs = D.blocked[3 * b + 1], be = D.blocked[3 * b + 2];
+    while (mk) {
+      const int i = __ffs(mk) - 1;
+      mk &= mk - 1;
+      const int si = st[i];
+      ok &= !(si < be && bs < si + D.dur[i]);
+    }
+  }
+  for (int o = 0; o < D.no; ++o) {
+    const int a = D.ordered[2 * o], b = D.ordered[2 * o + 1];
+    ok &= st[a] + D.dur[a] <= st[b];
+  }
+  return ok;
+}
+
+__device__ __forceinline__ float mt_cost(const MtLds& D, const unsigned* db) {
+#pragma clang fp contract(off)  // the twin rounds pc * w and the add separately
+  float num = 0.f, den = 0.f;
+  for (int q = 0; q < D.Q; ++q) {
+    unsigned mk = D.member[q];
+    if (!mk) continue;
+    const int nmeet = __popc(mk);
+    unsigned dm = 0;
+    int booked = 0;
+    while (mk) {
+      const int i = __ffs(mk) - 1;
+      mk &= mk - 1;
+      dm |= db[i];
+      booked += D.dur[i];
+    }
+    const int nday = __popc(dm);
+    const int free_q = 36000 * nday - booked, nslots = nmeet + nday;
+    const float pc = 8.f - ((float)free_q / (float)nslots) / 3600.f;
+    const float w = D.role_w[q];
+    const float pw = pc * w;
+    num = num + pw;
+    den = den + w;
+  }
+  return num / fmaxf(den, 1e-12f);
+}
+
+__global__ __launch_bounds__(64) void ga_meeting_kernel(
+    avk::GaMeetingDomain dom, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
+    float* __restrict__ hist, int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
+    long long island_base, unsigned long long gen_base) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gm_lds[];
+  const int M = dom.M, L = 3 * M, Ms = M | 1;  // Ms: odd stride of the lane-private rows
+  unsigned char* cur = gm_lds;
+  short* pa = reinterpret_cast<short*>(cur);  cur += mt_a16((size_t)P * L * sizeof(short));      // [P][L] pool
+  short* pb = reinterpret_cast<short*>(cur);  cur += mt_a16((size_t)P * L * sizeof(short));      // [P][L] next pool
+  short* kid = reinterpret_cast<short*>(cur); cur += mt_a16((size_t)2 * r * L * sizeof(short));  // [2r][L] children
+  float* pc = reinterpret_cast<float*>(cur);  cur += mt_a16((size_t)P * sizeof(float));
+  float* pc2 = reinterpret_cast<float*>(cur); cur += mt_a16((size_t)P * sizeof(float));
+  float* kc = reinterpret_cast<float*>(cur);  cur += mt_a16((size_t)2 * r * sizeof(float));
+  int* ord = reinterpret_cast<int*>(cur);     cur += mt_a16((size_t)P * sizeof(int));
+  int* kord = reinterpret_cast<int*>(cur);    cur += mt_a16((size_t)2 * r * sizeof(int));
+  int* nsrc = reinterpret_cast<int*>(cur);    cur += mt_a16((size_t)P * sizeof(int));
+  int* st_all = reinterpret_cast<int*>(cur);  cur += mt_a16((size_t)2 * r * Ms * sizeof(int));   // [2r][Ms] starts
+  unsigned* db_all = reinterpret_cast<unsigned*>(cur); cur += mt_a16((size_t)2 * r * Ms * sizeof(int));  // day bits
+  int* di = reinterpret_cast<int*>(cur);      // the domain, MT_DOM_INTS dwords
+  int* l_days = di;
+  int* l_hours = l_days + MT_MAX_CARD;
+  int* l_minutes = l_hours + MT_MAX_CARD;
+  int* l_dur = l_minutes + MT_MAX_CARD;
+  unsigned* l_share = reinterpret_cast<unsigned*>(l_dur + MT_MAX_M);
+  unsigned* l_member = l_share + MT_MAX_M;
+  float* l_role = reinterpret_cast<float*>(l_member + MT_MAX_Q);
+  int* l_blocked = reinterpret_cast<int*>(l_role + MT_MAX_Q);
+  int* l_ordered = l_blocked + 3 * MT_MAX_LIST;
+
+  const int lane = threadIdx.x;
+  const long long isl = blockIdx.x;
+  const unsigned long long gi = (unsigned long long)(island_base + isl);
+  if (lane < dom.nd) l_days[lane] = dom.days[lane];
+  if (lane < dom.nh) l_hours[lane] = dom.hours[lane];
+  if (lane < dom.nm) l_minutes[lane] = dom.minutes[lane];
+  if (lane < M) {
+    l_dur[lane] = dom.dur[lane];
+    l_share[lane] = dom.share[lane];
+  }
+  for (int q = lane; q < dom.Q; q += 64) {
+    l_member[q] = dom.member[q];
+    l_role[q] = dom.role_w[q];
+  }
+  if (lane < 3 * dom.nb) l_blocked[lane] = dom.blocked[lane];
+  if (lane < 2 * dom.no) l_ordered[lane] = dom.ordered[lane];
+  const MtLds D{l_days, l_hours, l_minutes, l_dur, l_blocked, l_ordered, l_share, l_member, l_role,
+                M, dom.Q, dom.nb, dom.no};
+  short* gpop = pop + isl * P * L;
+  for (int e = lane; e < P * L; e += 64) pa[e] = gpop[e];
+  if (lane < P) pc[lane] = pop_cost[isl * P + lane];
+  __syncthreads();
+  for (int g = 0; g < G; ++g) {
+    // 1. rank
+    ga_rank(pc, P, lane, ord);
+    __syncthreads();
+    if (lane == 0) hist[isl * G + g] = pc[ord[0]];
+    // 2 + 3. lane c: child c of pair c >> 1, built, mutated and priced
     if (lane < 2 * r) {
-      const float c = kc[lane];
-      int rk = 0;
-      for (int j = 0; j < 2 * r; ++j) rk += (kc[j] < c) || (kc[j] == c && j < lane);
-      kord[rk] = lane;
-    }
-    __syncthreads();
-    // 4. replacement: the source of every next-pool slot
-    if (purge_first) {
-      if (lane < P) nsrc[lane] = lane < P - r ? ord[lane] : P + kord[lane - (P - r)];
-    } else if (lane < P + r) {
-      // candidate lane: member ord-independent index (lane < P) or child kord[lane - P]; its rank
-      // among all candidates by (cost, candidate index)
-      const int src = lane < P ? lane : P + kord[lane - P];
-      const float c = lane < P ? pc[lane] : kc[src - P];
-      int rk = 0;
-      for (int j = 0; j < P + r; ++j) {
-        const int sj = j < P ? j : P + kord[j - P];
-        const float cj = j < P ? pc[j] : kc[sj - P];
-        rk += (cj < c) || (cj == c && j < lane);
+      const int h = lane & 1;
+      const unsigned long long ctr = 256ull * (gen_base + (unsigned long long)g) + (unsigned long long)(lane >> 1);
+      const av::u4 R = av::philox_draw(seed, ctr, gi);
+      const int a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
+      int b = 0;
+      if (m > 1) {
+        b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
+        b += b >= a;
       }
-      if (rk < P) nsrc[rk] = src;
+      const int cut = M > 1 ? 3 * (1 + min((int)(av::u32_to_unit(R.z) * (float)(M - 1)), M - 2)) : 0;
+      const short* A = pa + (size_t)ord[h ? b : a] * L;  // head of this child
+      const short* B = pa + (size_t)ord[h ? a : b] * L;  // tail
+      short* c = kid + (size_t)lane * L;
+      int* st = st_all + lane * Ms;
+      unsigned* db = db_all + lane * Ms;
+      for (int l = 0; l < L; ++l) c[l] = l < cut ? A[l] : B[l];
+      for (int i = 0; i < M; ++i) mt_place(D, c, i, st, db);
+      bool ok;
+      if (mutate) {
+        // one index to a different value of its table, redrawn up to GA_MAX_TRY times until the
+        // child is valid; the last attempt stays otherwise
+        for (int t = 0;; ++t) {
+          const av::u4 Q = av::philox_draw(seed ^ 0xD1B54A32D192ED03ull, ctr * 16ull + (unsigned long long)t, gi);
+          const unsigned qp = h == 0 ? Q.x : Q.z, qv = h == 0 ? Q.y : Q.w;
+          const int pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+          const int mi = pos / 3, comp = pos - 3 * mi;
+          const int card = comp == 0 ? dom.nd : comp == 1 ? dom.nh : dom.nm;
+          const int old = c[pos];
+          if (card > 1) {
+            int v = min((int)(av::u32_to_unit(qv) * (float)(card - 1)), card - 2);
+            v += v >= old;
+            c[pos] = (short)v;
+            mt_place(D, c, mi, st, db);
+          }
+          ok = mt_valid(D, st);
+          if (ok || t == GA_MAX_TRY - 1) break;
+          if (card > 1) {
+            c[pos] = (short)old;
+            mt_place(D, c, mi, st, db);
+          }
+        }
+      } else {
+        ok = mt_valid(D, st);
+      }
+      kc[lane] = ok ? mt_cost(D, db) : invalid;
     }
     __syncthreads();
-    for (int e = lane; e < P * L; e += 64) {
-      const int slot = e / L, l = e - slot * L;
-      const int src = nsrc[slot];
-      pb[e] = src < P ? pa[(size_t)src * L + l] : kid[(size_t)(src - P) * L + l];
-    }
-    if (lane < P) {
-      const int src = nsrc[lane];
-      pc2[lane] = src < P ? pc[src] : kc[src - P];
-    }
+    ga_rank(kc, 2 * r, lane, kord);
     __syncthreads();
+    // 4. replacement
+    ga_replace(pa, pb, kid, pc, pc2, kc, ord, kord, nsrc, P, L, r, purge_first, lane);
     short* t = pa; pa = pb; pb = t;
     float* tc = pc; pc = pc2; pc2 = tc;
   }
@@ -286,6 +502,33 @@ void ga_assign(const float* cost, int L, int V, const uint8_t* conflict, float i
   if (lds > 64 * 1024) throw std::invalid_argument("ga_assign: pool, children and costs exceed 64 KiB of LDS");
   ga_assign_kernel<<<islands, 64, lds, stream>>>(cost, L, V, conflict, invalid, pop, pop_cost, hist, P, G, m, r,
                                                  purge_first, mutate, swap, seed, island_base, gen_base);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+size_t ga_meeting_lds(int P, int L, int r) {
+  const size_t Ms = (size_t)(L / 3) | 1;
+  return 2 * mt_a16((size_t)P * L * sizeof(short)) + mt_a16((size_t)2 * r * L * sizeof(short)) +
+         4 * mt_a16((size_t)P * 4) + 2 * mt_a16((size_t)2 * r * 4) +  // pc, pc2, ord, nsrc; kc, kord
+         2 * mt_a16((size_t)2 * r * Ms * sizeof(int)) + mt_a16((size_t)MT_DOM_INTS * sizeof(int));
+}
+
+void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* pop_cost, float* hist, int islands,
+                int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
+                long long island_base, unsigned long long gen_base, hipStream_t stream) {
+  if (dom.M < 1 || dom.M > MT_MAX_M || dom.Q < 1 || dom.Q > MT_MAX_Q)
+    throw std::invalid_argument("ga_meeting: 1 <= M <= 32, 1 <= Q <= 256");
+  if (dom.nd < 1 || dom.nd > MT_MAX_CARD || dom.nh < 1 || dom.nh > MT_MAX_CARD || dom.nm < 1 || dom.nm > MT_MAX_CARD)
+    throw std::invalid_argument("ga_meeting: value tables of 1..32 entries");
+  if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
+    throw std::invalid_argument("ga_meeting: at most 16 blocked entries and 16 ordered pairs");
+  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P)
+    throw std::invalid_argument("ga_meeting: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
+  if (!purge_first && P + r > 64) throw std::invalid_argument("ga_meeting: P + r <= 64 when children join the pool");
+  const size_t lds = ga_meeting_lds(P, 3 * dom.M, r);
+  if (lds > 64 * 1024) throw std::invalid_argument("ga_meeting: pool, children and costs exceed 64 KiB of LDS");
+  if (islands <= 0 || G <= 0) return;
+  ga_meeting_kernel<<<islands, 64, lds, stream>>>(dom, invalid, pop, pop_cost, hist, P, G, m, r, purge_first, mutate,
+                                                  seed, island_base, gen_base);
   AV_HIP_CHECK(hipGetLastError());
 }
 

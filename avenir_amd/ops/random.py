@@ -11,12 +11,18 @@ _MASK = np.uint64(0xFFFFFFFF)
 
 
 def philox4x32(seed: int, offset: int, idx: np.ndarray) -> tuple[np.ndarray, ...]:
-    """Vectorised philox4x32-10 of counters (idx_lo, idx_hi, offset_lo, offset_hi) with key = seed."""
+    """Vectorised philox4x32-10 of counters (idx_lo, idx_hi, offset_lo, offset_hi) with key = seed.
+    ``offset`` is one int for all counters, or a uint64 array that broadcasts to the shape of ``idx``."""
     idx = np.asarray(idx, dtype=np.uint64)
     c0 = (idx & _MASK).astype(np.uint32)
     c1 = (idx >> np.uint64(32)).astype(np.uint32)
-    c2 = np.full_like(c0, np.uint32(offset & 0xFFFFFFFF))
-    c3 = np.full_like(c0, np.uint32((offset >> 32) & 0xFFFFFFFF))
+    if isinstance(offset, np.ndarray):                   # one offset per counter (uint64, shape of idx)
+        off = np.broadcast_to(offset.astype(np.uint64), idx.shape)
+        c2 = (off & _MASK).astype(np.uint32)
+        c3 = (off >> np.uint64(32)).astype(np.uint32)
+    else:
+        c2 = np.full_like(c0, np.uint32(offset & 0xFFFFFFFF))
+        c3 = np.full_like(c0, np.uint32((offset >> 32) & 0xFFFFFFFF))
     k0 = np.uint32(seed & 0xFFFFFFFF)
     k1 = np.uint32((seed >> 32) & 0xFFFFFFFF)
     with np.errstate(over="ignore"):

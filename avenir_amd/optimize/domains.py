@@ -149,7 +149,8 @@ class MeetingScheduleDomain(SearchDomain):
             parts.append(torch.randperm(n_people, generator=g)[:k].tolist())
         dvals, dw = [30, 60, 90, 120], torch.tensor([80.0, 100, 60, 40])
         durs = [dvals[int(i)] for i in torch.multinomial(dw, n_meetings, True, generator=g)]
-        order = [tuple(torch.randperm(n_meetings, generator=g)[:2].tolist())]
+        pair = torch.randperm(n_meetings, generator=g)[:2].tolist()
+        order = [tuple(pair)] if len(pair) == 2 else []      # a single meeting has no ordered pair
         blocked = {}
         for p in torch.randperm(n_people, generator=g)[:2].tolist():
             blocked[p] = (int(torch.randint(1, 6, (1,), generator=g)), int(torch.randint(8, 16, (1,), generator=g)),

@@ -1,0 +1,277 @@
+"""Island genetic algorithm over a meeting-schedule domain as ONE kernel launch (K22,
+``csrc/kernels/optim.hip::ga_meeting_kernel``) and its bit-exact host twin.
+
+Reference: the GA application of the reference is meeting scheduling (P/app/mesched.py driven by
+P/mlextra/optpopu.py:98-187).  The frame is the one of :mod:`~avenir_amd.optimize.ga`: every island
+is one workgroup whose pool, costs and children stay in LDS for all G generations of a launch, and
+its random stream is Philox keyed by the island's GLOBAL index.  What differs is the domain:
+
+* a solution is (day, hour, minute) index triples of M meetings into integer value tables;
+* validity is integer interval arithmetic (participant overlap, blocked hours, ordered pairs);
+* the cost is exact in integers up to one short fp32 reduction per solution, people in index order.
+
+:func:`meeting_tables` compiles a :class:`~avenir_amd.optimize.domains.MeetingScheduleDomain` into
+the kernel's tables (or ``None`` when it is outside the kernel's limits); :func:`ga_meeting_reference`
+replays the kernel in numpy — same Philox counters, same fp32 operations in the same order, same
+(cost, index) orderings — so GPU output equals it bit for bit.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..ops.random import philox4x32, u32_to_unit
+from .ga import _INIT_KEY, _MAX_TRY, _MUT_KEY, _unit_index
+
+MAX_M, MAX_Q, MAX_CARD, MAX_LIST = 32, 256, 32, 16      # the kernel's limits
+_TIME_LIMIT = 1 << 24                                     # seconds: exact in int32 and in fp32
+_F = np.float32
+
+
+def ga_meeting_lds(P: int, L: int, r: int) -> int:
+    """Bytes of LDS per island (``avk::ga_meeting_lds``): pools, children, costs, orders, the children's
+    start / day-bit rows and the staged domain, every array rounded up to 16 bytes."""
+    a16 = lambda n: (n + 15) & ~15
+    ms = (L // 3) | 1
+    return (2 * a16(2 * P * L) + a16(4 * r * L) + 4 * a16(4 * P) + 2 * a16(8 * r) + 2 * a16(8 * r * ms)
+            + a16(4 * (3 * MAX_CARD + 2 * MAX_M + 2 * MAX_Q + 5 * MAX_LIST)))
+
+
+def _int_values(t) -> np.ndarray | None:
+    v = np.asarray(torch.as_tensor(t).detach().cpu().double().numpy(), dtype=np.float64).reshape(-1)
+    if not np.isfinite(v).all():
+        return None
+    r = np.rint(v)
+    if not np.array_equal(r, v) or np.abs(r).max(initial=0) >= _TIME_LIMIT:
+        return None
+    return r.astype(np.int64)
+
+
+def _masks(rows: np.ndarray) -> np.ndarray:
+    """bool [n, M] -> one 32-bit mask per row (bit j = column j), stored as int32."""
+    w = np.uint64(1) << np.arange(rows.shape[1], dtype=np.uint64)
+    return (rows.astype(np.uint64) * w[None, :]).sum(1).astype(np.uint32).view(np.int32)
+
+
+def meeting_tables(domain) -> dict | None:
+    """The kernel's integer tables and masks of a MeetingScheduleDomain, or ``None`` when the domain
+    is outside the kernel's limits (M <= 32, Q <= 256, value tables <= 32, <= 16 blocked entries and
+    ordered pairs, all times whole seconds below 2^24) or is no MeetingScheduleDomain."""
+    from .domains import MeetingScheduleDomain
+    if not isinstance(domain, MeetingScheduleDomain):
+        return None
+    days, hours, minutes, dur = (_int_values(x) for x in (domain.days, domain.hours, domain.minutes, domain.dur))
+    if any(x is None or x.size == 0 for x in (days, hours, minutes, dur)):
+        return None
+    member = domain.member.cpu().numpy().astype(bool)                     # [Q, M]
+    Q, M = member.shape
+    if not (1 <= M <= MAX_M and 1 <= Q <= MAX_Q and dur.size == M):
+        return None
+    if max(days.size, hours.size, minutes.size) > MAX_CARD:
+        return None
+    if days.min() < 1 or hours.min() < 0 or minutes.min() < 0 or dur.min() < 0:
+        return None
+    if (days.max() - 1) * 86400 + hours.max() * 3600 + minutes.max() * 60 + dur.max() >= _TIME_LIMIT:
+        return None
+    share = domain.share.cpu().numpy().astype(bool)
+    share = (share | share.T) & ~np.eye(M, dtype=bool)
+    blocked = []
+    for p, spec in domain.blocked.items():
+        b = _int_values(list(spec))
+        if b is None or b.size != 3 or not 0 <= int(p) < Q:
+            return None
+        bs = (b[0] - 1) * 86400 + b[1] * 3600
+        be = bs + b[2] * 3600
+        if not 0 <= bs <= be < _TIME_LIMIT:
+            return None
+        blocked.append((int(_masks(member[int(p)][None, :])[0]), int(bs), int(be)))
+    if any(len(p) != 2 for p in domain.ordered):
+        return None
+    ordered = [(int(a), int(b)) for a, b in domain.ordered]
+    if len(blocked) > MAX_LIST or len(ordered) > MAX_LIST or any(not (0 <= a < M and 0 <= b < M) for a, b in ordered):
+        return None
+    role_w = domain.role_w.detach().cpu().numpy().astype(np.float32).reshape(-1)
+    if role_w.size != Q:
+        return None
+    return {
+        "M": M, "Q": Q, "L": 3 * M,
+        "days": days.astype(np.int32), "hours": hours.astype(np.int32), "minutes": minutes.astype(np.int32),
+        "dur": dur.astype(np.int32), "share": _masks(share), "member": _masks(member), "role_w": role_w,
+        "blocked": np.array(blocked, dtype=np.int32).reshape(-1, 3),
+        "ordered": np.array(ordered, dtype=np.int32).reshape(-1, 2),
+        "cards": np.array([days.size, hours.size, minutes.size] * M, dtype=np.int64),
+        "share_b": share, "member_b": member, "invalid": float(domain.invalid_cost),
+    }
+
+
+def _times(tb: dict, sol: np.ndarray):
+    s = np.asarray(sol, dtype=np.int64)
+    st = ((tb["days"].astype(np.int64)[s[..., 0::3]] - 1) * 86400 + tb["hours"].astype(np.int64)[s[..., 1::3]] * 3600
+          + tb["minutes"].astype(np.int64)[s[..., 2::3]] * 60)
+    return st, st + tb["dur"].astype(np.int64)
+
+
+def ga_meeting_valid(tables: dict, sol: np.ndarray) -> np.ndarray:
+    """Validity of sol [..., 3 M] index triples -> bool [...], integers only (the kernel's ``mt_valid``)."""
+    st, en = _times(tables, sol)
+    M = tables["M"]
+    overlap = (st[..., :, None] < en[..., None, :]) & (st[..., None, :] < en[..., :, None])
+    ok = ~(overlap & tables["share_b"]).any(axis=(-1, -2))
+    bits = np.arange(M)
+    for mask, bs, be in tables["blocked"].tolist():
+        mine = ((np.uint32(mask & 0xFFFFFFFF) >> bits.astype(np.uint32)) & np.uint32(1)).astype(bool)
+        ok &= ~((st < be) & (bs < en) & mine).any(-1)
+    for a, b in tables["ordered"].tolist():
+        ok &= en[..., a] <= st[..., b]
+    return ok
+
+
+def ga_meeting_price(tables: dict, sol: np.ndarray) -> np.ndarray:
+    """Cost of sol [..., 3 M] -> float32 [...], ``inf`` (the domain's invalid cost) on invalid rows.
+    Per person q and day: cnt meetings and booked seconds; over the days with a meeting
+    free_q = sum(36000 - booked), nslots_q = sum(cnt + 1), both integers;
+    pc = 8 - (free_q / nslots_q) / 3600 and cost = sum(pc w_q) / max(sum(w_q), 1e-12) in fp32,
+    accumulated with q ascending, product and sum rounded separately — the kernel's ``mt_cost``."""
+    s = np.asarray(sol, dtype=np.int64)
+    nd = tables["days"].size
+    # float64 products of small integers are exact (and take the BLAS path)
+    onehot = (s[..., 0::3, None] == np.arange(nd)).astype(np.float64)                # [..., M, nd]
+    mem = tables["member_b"].astype(np.float64)                                      # [Q, M]
+    cnt = np.matmul(mem, onehot).astype(np.int64)                                    # [..., Q, nd]
+    booked = np.matmul(mem, onehot * tables["dur"].astype(np.float64)[:, None]).astype(np.int64)
+    active = cnt > 0
+    free = np.where(active, 36000 - booked, 0).sum(-1)                               # [..., Q]
+    nslots = np.where(active, cnt + 1, 0).sum(-1)
+    num = np.zeros(s.shape[:-1], dtype=np.float32)
+    den = np.zeros(s.shape[:-1], dtype=np.float32)
+    for q in range(tables["Q"]):
+        has = nslots[..., q] > 0
+        pc = _F(8.0) - (free[..., q].astype(np.float32) / np.maximum(nslots[..., q], 1).astype(np.float32)) / _F(3600.0)
+        w = _F(tables["role_w"][q])
+        num = np.where(has, num + pc * w, num).astype(np.float32)
+        den = np.where(has, den + w, den).astype(np.float32)
+    cost = (num / np.maximum(den, _F(1e-12))).astype(np.float32)
+    return np.where(ga_meeting_valid(tables, s), cost, _F(tables["invalid"])).astype(np.float32)
+
+
+def ga_meeting_init(tables: dict, n_islands: int, P: int, seed: int, island_base: int, max_try: int = 40) -> np.ndarray:
+    """Initial pools [islands, P, 3 M] int16, host-side per global island: member p of island gi,
+    attempt a, position l is min((int)(u card_l), card_l - 1) with u from
+    Philox(seed ^ INIT, (p L + l) 64 + a, gi).x; the whole member is redrawn while it is invalid (up
+    to ``max_try`` <= 64 attempts, the last one stays)."""
+    if not 1 <= max_try <= 64:
+        raise ValueError("max_try must lie in [1, 64]")
+    L, cards = tables["L"], tables["cards"]
+    out = np.zeros((n_islands, P, L), dtype=np.int64)
+    ti, tp = (x.reshape(-1) for x in np.meshgrid(np.arange(n_islands), np.arange(P), indexing="ij"))
+    pos = np.arange(L, dtype=np.uint64)[None, :]
+    for a in range(max_try):
+        if ti.size == 0:
+            break
+        off = (tp.astype(np.uint64)[:, None] * np.uint64(L) + pos) * np.uint64(64) + np.uint64(a)
+        gis = np.broadcast_to((ti + island_base).astype(np.uint64)[:, None], off.shape)
+        x, _, _, _ = philox4x32(seed ^ _INIT_KEY, off, gis)
+        draw = np.minimum((u32_to_unit(x) * cards.astype(np.float32)[None, :]).astype(np.int64), cards[None, :] - 1)
+        out[ti, tp] = draw
+        bad = ~ga_meeting_valid(tables, draw)
+        ti, tp = ti[bad], tp[bad]
+    return out.astype(np.int16)
+
+
+def ga_meeting_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
+                         purge_first: bool, mutate: bool, seed: int, island_base: int,
+                         gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host twin of ``ga_meeting_kernel`` (all islands at once).  Returns (pop int16, cost float32,
+    hist float32)."""
+    pop = np.array(pop, dtype=np.int64)
+    pc = np.array(pop_cost, dtype=np.float32)
+    I, P, L = pop.shape
+    M, cards = tables["M"], tables["cards"]
+    gis = np.arange(island_base, island_base + I, dtype=np.uint64)
+    ar = np.arange(I)
+    ii = ar[:, None]
+    kk = np.arange(r)[None, :]
+    gir = np.broadcast_to(gis[:, None], (I, r))
+    hist = np.zeros((I, G), dtype=np.float32)
+    for g in range(G):
+        ord_ = np.argsort(pc, axis=1, kind="stable")
+        hist[:, g] = pc[ar, ord_[:, 0]]
+        # all r pairs of all islands at once: arrays [I, r]
+        ctr = np.array([256 * (gen_base + g) + k for k in range(r)], dtype=np.uint64)[None, :]
+        x_, y_, z_, _ = philox4x32(seed, np.broadcast_to(ctr, (I, r)), gir)
+        a = _unit_index(u32_to_unit(x_), m)
+        b = np.zeros((I, r), dtype=np.int64)
+        if m > 1:
+            b = np.minimum((u32_to_unit(y_) * _F(m - 1)).astype(np.int64), m - 2)
+            b = b + (b >= a)
+        cut = np.zeros((I, r), dtype=np.int64)
+        if M > 1:                                                # the cut falls between two meetings
+            cut = 3 * (1 + np.minimum((u32_to_unit(z_) * _F(M - 1)).astype(np.int64), M - 2))
+        A = pop[ii, ord_[ii, a]]                                 # [I, r, L]
+        B = pop[ii, ord_[ii, b]]
+        left = np.arange(L)[None, None, :] < cut[:, :, None]
+        pair = [np.where(left, A, B), np.where(left, B, A)]
+        if mutate:
+            for h, c in enumerate(pair):
+                done = np.zeros((I, r), dtype=bool)
+                for t in range(_MAX_TRY):
+                    if done.all():
+                        break
+                    q = philox4x32(seed ^ _MUT_KEY, np.broadcast_to(ctr * np.uint64(16) + np.uint64(t), (I, r)), gir)
+                    qp, qv = (q[0], q[1]) if h == 0 else (q[2], q[3])
+                    pos = _unit_index(u32_to_unit(qp), L)
+                    old = c[ii, kk, pos]
+                    card = cards[pos]
+                    v = np.minimum((u32_to_unit(qv) * np.maximum(card - 1, 1).astype(np.float32)).astype(np.int64),
+                                   np.maximum(card - 2, 0))
+                    v = np.where(card > 1, v + (v >= old), old)          # a one-value table keeps its value
+                    cand = c.copy()
+                    cand[ii, kk, pos] = v
+                    take = ~done & ((t == _MAX_TRY - 1) | ga_meeting_valid(tables, cand))
+                    c[take] = cand[take]
+                    done |= take
+        kids = np.stack(pair, axis=2).reshape(I, 2 * r, L)           # child 2k, 2k + 1 of pair k
+        kc = ga_meeting_price(tables, kids)
+        kord = np.argsort(kc, axis=1, kind="stable")
+        if purge_first:
+            nsrc = np.concatenate([ord_[:, : P - r], P + kord[:, :r]], axis=1)
+        else:
+            src = np.concatenate([np.broadcast_to(np.arange(P), (I, P)), P + kord[:, :r]], axis=1)
+            cc = np.concatenate([pc, kc[ii, kord[:, :r]]], axis=1)
+            nsrc = np.take_along_axis(src, np.argsort(cc, axis=1, kind="stable")[:, :P], axis=1)
+        allp = np.concatenate([pop, kids], axis=1)
+        allc = np.concatenate([pc, kc], axis=1)
+        pop = allp[ii, nsrc]
+        pc = allc[ii, nsrc]
+    return pop.astype(np.int16), pc, hist
+
+
+_DEV_KEYS = ("days", "hours", "minutes", "dur", "share", "member", "role_w", "blocked", "ordered")
+
+
+def _device_tables(tables: dict, device: torch.device) -> list[torch.Tensor]:
+    cache = tables.setdefault("_device", {})
+    key = str(device)
+    if key not in cache:
+        cache[key] = [torch.from_numpy(np.ascontiguousarray(tables[k])).to(device) for k in _DEV_KEYS]
+    return cache[key]
+
+
+def ga_meeting_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool,
+                   mutate: bool, seed: int, island_base: int, device: torch.device, gen_base: int = 0):
+    """Advance the islands G generations (counters from ``gen_base``) on ``device``: the kernel on the
+    GPU, the twin on the host.  ``domain`` is a MeetingScheduleDomain or its :func:`meeting_tables`.
+    Returns numpy (pop, pop_cost, hist)."""
+    tables = domain if isinstance(domain, dict) else meeting_tables(domain)
+    if tables is None:
+        raise ValueError("the domain is outside the meeting kernel's limits")
+    device = torch.device(device)
+    if device.type == "cuda":
+        from .. import _native
+        tp = torch.from_numpy(np.ascontiguousarray(pop, dtype=np.int16)).to(device)
+        tc = torch.from_numpy(np.ascontiguousarray(pop_cost, dtype=np.float32)).to(device)
+        hist = torch.empty((pop.shape[0], G), dtype=torch.float32, device=device)
+        _native.C().ga_meeting(*_device_tables(tables, device), float(tables["invalid"]), tp, tc, hist, G, m, r,
+                               bool(purge_first), bool(mutate), int(seed), int(island_base), int(gen_base))
+        return tp.cpu().numpy(), tc.cpu().numpy(), hist.cpu().numpy()
+    return ga_meeting_reference(tables, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)

@@ -388,6 +388,52 @@ def local_trajectory(d: SearchDomain, sols: torch.Tensor, costs: torch.Tensor, n
 # ================================================================================================
 # population optimisers
 # ================================================================================================
+class _AssignIslands:
+    """Island engine of an AssignmentDomain: ``ga_assign_kernel`` / its twin (optimize/ga.py)."""
+
+    def __init__(self, domain):
+        self.d = domain
+
+    def name(self, device) -> str:
+        return "ga_assign_kernel" if device.type == "cuda" else "ga_twin"
+
+    def init(self, n: int, P: int, seed: int, island_base: int):
+        from .ga import ga_init_population, ga_price
+        d = self.d
+        conf = None
+        if d.conflict is not None:
+            c = d.conflict.cpu().numpy()
+            conf = np.triu(c, 1) | np.triu(c, 1).T
+        pop = ga_init_population(n, P, d.L, d.V, seed, island_base, conf)
+        cost = ga_price(d.cost_table.cpu().numpy().astype(np.float32), conf, d.invalid_cost, pop.astype(np.int64))
+        return pop, cost
+
+    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
+        from .ga import ga_assign_run
+        return ga_assign_run(self.d, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
+                             gen_base=gen_base)
+
+
+class _MeetingIslands:
+    """Island engine of a MeetingScheduleDomain: ``ga_meeting_kernel`` / its twin (optimize/ga_meeting.py)."""
+
+    def __init__(self, tables: dict):
+        self.tables = tables
+
+    def name(self, device) -> str:
+        return "ga_meeting_kernel" if device.type == "cuda" else "ga_meeting_twin"
+
+    def init(self, n: int, P: int, seed: int, island_base: int):
+        from .ga_meeting import ga_meeting_init, ga_meeting_price
+        pop = ga_meeting_init(self.tables, n, P, seed, island_base)
+        return pop, ga_meeting_price(self.tables, pop)
+
+    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
+        from .ga_meeting import ga_meeting_run
+        return ga_meeting_run(self.tables, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
+                              gen_base=gen_base)
+
+
 class GeneticAlgorithm:
     """Island-model GA: ``islands`` independent pools advance together as one [I, pool, L] batch.
 
@@ -424,8 +470,9 @@ class GeneticAlgorithm:
         written by rank 0 — resumes at ANY world size by re-dealing the islands by global index."""
         from ..data.table import shard_range
         comm = self.comm or get_comm()
-        if self._kernel_ok():
-            return self._run_islands(comm)
+        engine = self._island_engine()
+        if engine is not None:
+            return self._run_islands(comm, engine)
         d, Pp, L = self.d, self.Pp, self.d.L
         W, r = comm.world, comm.rank
         lp = IterationLoop("geneticAlgorithm", self.recovery, comm, device=d.device)
@@ -467,43 +514,46 @@ class GeneticAlgorithm:
         b, c = _global_best(comm, bc, bs)
         return OptResult(b, c, bc, bs, history)
 
-    def _kernel_ok(self) -> bool:
-        """The one-launch island kernel (optimize/ga.py): assignment domains without tied groups
-        or checkpointing, pools of <= 64, LDS <= 64 KiB per island; on the CPU its host twin."""
+    def _island_engine(self):
+        """The one-launch island kernel that applies to this run, or None (the generic torch path):
+        no tied groups or checkpointing, pools of <= 64, LDS <= 64 KiB per island.  Assignment
+        domains take ``ga_assign_kernel`` (optimize/ga.py), on the CPU its host twin.  Meeting-schedule
+        domains within the kernel's limits take ``ga_meeting_kernel`` (optimize/ga_meeting.py) on a
+        GPU; on the CPU its twin runs only when ``use_kernel`` is True, so CPU results are unchanged."""
         d = self.d
-        if self.use_kernel is False or not isinstance(d, AssignmentDomain) or getattr(d, "groups", None):
-            return False
-        if self.recovery is not None:
-            return False
+        if self.use_kernel is False or getattr(d, "groups", None) or self.recovery is not None:
+            return None
         P, r, m = self.Pp, self.r, self.m
         if not (2 <= P <= 64 and 1 <= r <= min(P, 32) and 1 <= m <= P and (self.purge_first or P + r <= 64)):
-            return False
-        lds = (2 * P + 2 * r) * d.L * 2 + (2 * P + 2 * r) * 8
-        return lds <= 64 * 1024 and d.V <= 32767
+            return None
+        if isinstance(d, AssignmentDomain):
+            lds = (2 * P + 2 * r) * d.L * 2 + (2 * P + 2 * r) * 8
+            return _AssignIslands(d) if lds <= 64 * 1024 and d.V <= 32767 else None
+        if self.use_kernel is True or d.device.type == "cuda":
+            from .ga_meeting import ga_meeting_lds, meeting_tables
+            tables = meeting_tables(d)      # None unless a MeetingScheduleDomain within the kernel's limits
+            if tables is not None and ga_meeting_lds(P, d.L, r) <= 64 * 1024:
+                return _MeetingIslands(tables)
+        return None
 
-    def _run_islands(self, comm) -> OptResult:
+    def _run_islands(self, comm, engine) -> OptResult:
         """All of this rank's islands, G generations, in one kernel launch (per migration interval):
         islands [r * islands, (r + 1) * islands) by GLOBAL index, so the W-rank run equals one
         process running W * islands; migration (ring of elites) runs on host copies between
-        launches, identically on either device."""
-        from .ga import ga_assign_run, ga_init_population, ga_price
+        launches, identically on either device.  ``engine`` supplies the initial pools and advances
+        them (the kernel on the GPU, its twin on the host)."""
         d = self.d
         W, rk = comm.world, comm.rank
         a, e = rk * self.I, (rk + 1) * self.I
         total = self.I * W
-        conf = None
-        if d.conflict is not None:
-            c = d.conflict.cpu().numpy()
-            conf = np.triu(c, 1) | np.triu(c, 1).T
-        pop = ga_init_population(e - a, self.Pp, d.L, d.V, self.seed, a, conf)
-        cost = ga_price(d.cost_table.cpu().numpy().astype(np.float32), conf, d.invalid_cost, pop.astype(np.int64))
+        pop, cost = engine.init(e - a, self.Pp, self.seed, a)
         step = self.migrate_every if (self.migrate_every and total > 1) else self.G
         hists = []
         g = 0
         while g < self.G:
             k = min(step, self.G - g)
-            pop, cost, h = ga_assign_run(d, pop, cost, k, self.m, self.r, self.purge_first, self.mutate_children,
-                                         self.seed, a, d.device, gen_base=g)
+            pop, cost, h = engine.run(pop, cost, k, self.m, self.r, self.purge_first, self.mutate_children,
+                                      self.seed, a, d.device, gen_base=g)
             hists.append(h)
             g += k
             if g < self.G and step < self.G:
@@ -517,7 +567,7 @@ class GeneticAlgorithm:
         bs = torch.from_numpy(pop[ii, bi].astype(np.int64)).to(d.device)
         bc = torch.from_numpy(cost[ii, bi]).to(d.device)
         b, c = _global_best(comm, bc, bs)
-        return OptResult(b, c, bc, bs, history, {"engine": "ga_assign_kernel" if d.device.type == "cuda" else "ga_twin"})
+        return OptResult(b, c, bc, bs, history, {"engine": engine.name(d.device)})
 
     @staticmethod
     def _migrate(comm, pop, cost, a, e):
