@@ -351,10 +351,16 @@ __global__ __launch_bounds__(KB) void kmeans_mfma_kernel(const float* __restrict
 //     fragment the matching terms: [x0|x1].[c0|c0] + [x0|x1].[c1|c1] + [x0|x2].[c2|c0] = the 6
 //     cross products of fp32-level accuracy (SB = 3) in 3 MFMAs per 16 rows x 16 dims; SB = 2
 //     keeps [x0|x1].[c0|c0] + [x0|x1].[c1|0] (2 MFMAs, ~2^-17 per product);
-//   partial sums: the one-hot is exact in bf16, the staged rows go in as [x0|x1] over 4 rows per
-//     row group: 16 rows per MFMA, 4 per tile instead of 16 (x0 + x1 carries ~2^-18 relative of
-//     each summed coordinate).
-// Per tile 12 + 4 bf16 MFMAs of 16 cycles (256) instead of 32 fp32 ones of 32 (1,024).
+//   partial sums: the one-hot is exact in bf16 and the staged rows go in as all three terms, whose
+//     sum IS the fp32 value (3 x 8 significand bits, RNE remainders): [x0|x1] over 4 rows per row
+//     group (16 rows per MFMA, 4 per tile) plus [x2|x2] over 8 rows per row group (32 rows per MFMA,
+//     2 per tile) instead of 16 fp32 MFMAs.  Every product is exact and the accumulation is fp32,
+//     so in every mode (SB = 0, 2, 3) the workgroup partial sums are fp32 sums of the fp32 data;
+//     only the SCORES differ by mode (fp32; ~2^-17 per product for SB = 2; fp32-level for SB = 3).
+//     Two terms would not do: they keep 16-17 significand bits, and a feature that is nearly
+//     constant within a cluster (cents, epoch seconds) loses the SAME low bits in every row, an
+//     error that does not average out and that kmeans_update_kernel divides into the centroids.
+// Per tile 12 + 6 bf16 MFMAs of 16 cycles (288) instead of 32 fp32 ones of 32 (1,024).
 template <int D, int KBLK, int NBUF, int SB = 0>
 __global__ __launch_bounds__(KB, (KBLK == 1 && D <= 16) ? (NBUF == 2 ? 4 : 3) : 2) void kmeans_score_kernel(const float* __restrict__ X, long long n,
                                                           const float* __restrict__ C2, const float* __restrict__ Cn,
@@ -562,6 +568,8 @@ __global__ __launch_bounds__(KB, (KBLK == 1 && D <= 16) ? (NBUF == 2 ? 4 : 3) : 
     // wave-private strip: LDS executes one wave's instructions in order
     __builtin_amdgcn_wave_barrier();
     const float* xr = xs + 16 * grp * RS + 16 * grp + col;  // row 16 grp, dim col
+    // split-bf16: the third terms (and one-hot halves) of the even steps wait for the odd ones
+    unsigned x2k[DB][2], ohk[KBLK][2];
 #pragma unroll
     for (int s0 = 0; s0 < 16; s0 += 4) {
       const int4 a4 = *reinterpret_cast<const int4*>(asg + 16 * grp + s0);
@@ -582,13 +590,22 @@ __global__ __launch_bounds__(KB, (KBLK == 1 && D <= 16) ? (NBUF == 2 ? 4 : 3) : 
               acc[q & 1][cb][db] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bb[q][db], acc[q & 1][cb][db], 0, 0, 0);
           }
       } else {
-        // k-slot 8 grp + j: row 16 grp + s0 + (j & 3), term j >> 2 (one-hot repeated: exact in bf16)
-        bf16x8 xb[DB];
+        // [x0|x1] MFMA, k-slot 8 grp + j: row 16 grp + s0 + (j & 3), term j >> 2 (one-hot repeated:
+        // exact in bf16).  x0 + x1 + x2 IS the fp32 value (three RNE bf16 terms hold 24 significand
+        // bits), so the third terms go in too: [x2 of the previous step's 4 rows|x2 of this step's]
+        // every second step, k-slot j: row 16 grp + s0 - 4 + j.
+        bf16x8 xb[DB], x2b[DB];
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
-          unsigned xt[2][2];
-          km_split4<2>(bb[0][db], bb[1][db], bb[2][db], bb[3][db], xt);
+          unsigned xt[3][2];
+          km_split4<3>(bb[0][db], bb[1][db], bb[2][db], bb[3][db], xt);
           xb[db] = km_frag(xt[0][0], xt[0][1], xt[1][0], xt[1][1]);
+          if ((s0 >> 2) & 1) {
+            x2b[db] = km_frag(x2k[db][0], x2k[db][1], xt[2][0], xt[2][1]);
+          } else {
+            x2k[db][0] = xt[2][0];
+            x2k[db][1] = xt[2][1];
+          }
         }
 #pragma unroll
         for (int cb = 0; cb < KBLK; ++cb) {
@@ -599,6 +616,15 @@ __global__ __launch_bounds__(KB, (KBLK == 1 && D <= 16) ? (NBUF == 2 ? 4 : 3) : 
 #pragma unroll
           for (int db = 0; db < DB; ++db)
             acc[(s0 >> 2) & 1][cb][db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oh, xb[db], acc[(s0 >> 2) & 1][cb][db], 0, 0, 0);
+          if ((s0 >> 2) & 1) {
+            const bf16x8 oh2 = km_frag(ohk[cb][0], ohk[cb][1], h0, h1);
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+              acc[(s0 >> 3) & 1][cb][db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oh2, x2b[db], acc[(s0 >> 3) & 1][cb][db], 0, 0, 0);
+          } else {
+            ohk[cb][0] = h0;
+            ohk[cb][1] = h1;
+          }
         }
       }
     }
@@ -761,8 +787,15 @@ KmVariant km_variant(int D, int K, int R) {
     return e && (e[0] == 'v' || e[0] == 'V');  // "valu": the packed-FMA scoring kernel (A/B)
   }();
   // AVMI_KMEANS_MFMA = f32 | bf16x3 (default) | bf16x6: the arithmetic of kmeans_score_kernel.
-  // At 16.7 M x 16, k = 16: f32 253.5 us, x3 199.6 us, x6 217.1 us per pass; x3 passes the fp64
-  // oracle with its fp32 tie tolerance (profiles/r6_kmeans_split_bf16.jsonl, r6_kmeans_tests_bf16x3.log)
+  // Scoring accuracy by mode: f32 = fp32 products and sums; x3 ~2^-17 relative per product (passes
+  // the fp64 oracle with its fp32 tie tolerance); x6 fp32-level.  The partial sums are fp32 sums of
+  // the fp32 data in ALL modes (three bf16 terms in the one-hot MFMA; the cross-workgroup reduce is
+  // fp64), and integer data that fits one bf16 term is reproduced bit for bit by every mode
+  // (tests/test_kmeans_kernels.py).
+  // At 16.7 M x 16, k = 16, kernel time: f32 253.5 us, x3 199.6 us, x6 217.1 us per pass with
+  // two-term sums (profiles/r6_kmeans_split_bf16.jsonl).  The third term, as kmeans_assign call
+  // time (median of 1000 warm passes, device events): x3 193.4 -> 201.2 us (+4 %), x6 211.4 ->
+  // 229.2 us (+8 %) (profiles/kmeans_exact_sums_pass_times.jsonl); f32 is unchanged.
   static const int sbm = [] {
     const char* e = std::getenv("AVMI_KMEANS_MFMA");
     if (e == nullptr) return 2;

@@ -169,6 +169,7 @@ class KMeans:
         self.recovery = recovery           # checkpoint / resume per Lloyd iteration (utils/resilience)
         self.runs: list[KMeansRun] = []
         self.best: dict[int, KMeansRun] = {}
+        self._shift: torch.Tensor | None = None   # GPU fits: the feature translation of the passes
 
     # ------------------------------------------------------------------------------------------
     def _seed_sample(self, X: torch.Tensor, g: torch.Generator, comm) -> torch.Tensor:
@@ -251,7 +252,8 @@ class KMeans:
         return res
 
     @staticmethod
-    def _padded(X: torch.Tensor) -> torch.Tensor | None:
+    def _padded(X: torch.Tensor, shift: torch.Tensor | None = None) -> torch.Tensor | None:
+        """``X - shift`` with D zero-padded to the kernels' 2/4/8/16/32/64 (None: no GPU path)."""
         if not X.is_cuda or not _native.available():
             return None
         D = X.shape[1]
@@ -259,9 +261,12 @@ class KMeans:
         if Dp is None:
             return None
         if Dp == D:
-            return X
+            return X if shift is None else X - shift
         Xp = torch.zeros((X.shape[0], Dp), dtype=torch.float32, device=X.device)
-        Xp[:, :D] = X
+        if shift is None:
+            Xp[:, :D] = X
+        else:
+            torch.sub(X, shift, out=Xp[:, :D])
         return Xp
 
     def _groups(self, specs: list[tuple[int, int]], Dp: int | None) -> list[list[int]]:
@@ -291,17 +296,28 @@ class KMeans:
         distributed, one update launch and a 4-byte-per-run host read of the centroid movement."""
         comm = self.comm or get_comm()
         X = X.float().contiguous()
-        self._tol_eff = self._effective_tol(X, comm)
-        Xp = self._padded(X)
+        mean, self._tol_eff = self._feature_stats(X, comm, want_mean=X.is_cuda)
         specs = self.run_specs()
         if init_centroids is None:                 # (``init_centroids``: from init_many)
             init_centroids = self._init_centroids_all(X, specs)
+        # GPU: the kernels score with ||c||^2 - 2 x.c in fp32, whose rounding error grows with the
+        # square of a common feature offset (a year, an amount) and soon exceeds the cluster
+        # separation, so the Lloyd passes run on X - shift; the shift is the all-reduced feature
+        # mean (one value per fit, identical on every rank and on a resumed fit) and the centroids
+        # are translated back below.  The CPU path scores with fp64 direct distances.
+        Xp = self._padded(X, mean.float() if X.is_cuda else None)
+        self._shift = mean.float() if Xp is not None else None
         runs = [KMeansRun(k, sd, C) for (k, sd), C in zip(specs, init_centroids)]
         self.best = {}
         for gi, grp in enumerate(self._groups(specs, Xp.shape[1] if Xp is not None else None)):
             with IterationLoop(f"kmeans.g{gi}", self.recovery, comm, device=X.device) as lp:
                 if Xp is not None:
-                    self._fit_gpu_group(X.shape[1], Xp, [runs[i] for i in grp], comm, lp)
+                    sub = [runs[i] for i in grp]
+                    for r in sub:
+                        r.centroids = r.centroids.float().to(X.device) - self._shift
+                    self._fit_gpu_group(X.shape[1], Xp, sub, comm, lp)
+                    for r in sub:
+                        r.centroids = r.centroids + self._shift
                 else:
                     self._fit_cpu_group(X, [runs[i] for i in grp], comm, lp)
         self.runs = runs
@@ -310,18 +326,25 @@ class KMeans:
                 self.best[r.k] = r
         return self
 
-    def _effective_tol(self, X: torch.Tensor, comm) -> float:
-        if self.tol_mode == "shift":
-            return self.tol
-        # global mean of per-feature variances (sums / squares / count all-reduced)
-        st = torch.stack([X.double().sum(0), (X.double() ** 2).sum(0)])
+    def _feature_stats(self, X: torch.Tensor, comm, want_mean: bool):
+        """(global per-feature mean f64 [D] or None, effective tolerance) from ONE all-reduce of the
+        per-feature sums / squares / count: the same values on every rank."""
+        sklearn = self.tol_mode == "sklearn"
+        if not (want_mean or sklearn):
+            return None, self.tol
+        st = torch.stack([X.sum(0, dtype=torch.float64),
+                          (X.double() ** 2).sum(0) if sklearn else torch.zeros(X.shape[1], dtype=torch.float64,
+                                                                                device=X.device)])
         n = torch.tensor([float(X.shape[0])], dtype=torch.float64, device=X.device)
         if comm.is_distributed:
             comm.all_reduce(st)
             comm.all_reduce(n)
         mean = st[0] / n
+        if not sklearn:
+            return mean, self.tol
+        # global mean of per-feature variances
         var = (st[1] / n - mean * mean).clamp_min(0)
-        return float(var.mean()) * self.tol
+        return mean, float(var.mean()) * self.tol
 
     def _converged(self, max_shift: float, sq_shift: float) -> bool:
         if self.tol_mode == "shift":
@@ -444,8 +467,13 @@ class KMeans:
         return self.best[self.ks[0]].centroids
 
     def predict(self, X: torch.Tensor, k: int | None = None) -> torch.Tensor:
-        C = self.best[k or self.ks[0]].centroids
-        return dist.knn(X.float(), C.to(X.device), 1, "sqeuclidean")[1][:, 0]
+        C = self.best[k or self.ks[0]].centroids.to(X.device)
+        X = X.float()
+        shift = self._shift
+        if shift is not None:                     # the fit's translation: same scores as its passes
+            shift = shift.to(X.device)
+            X, C = X - shift, C - shift
+        return dist.knn(X, C, 1, "sqeuclidean")[1][:, 0]
 
     def knuckle_k(self) -> int:
         """k at the maximum second difference of min-SSE vs k (MathUtils.getMaxSecondDiff)."""
