@@ -266,6 +266,11 @@ void class_histogram_radix(const at::Tensor& dense, int64_t n, int64_t B, std::v
                              cur_stream(dense));
 }
 
+int64_t radix_recip(int64_t d) {
+  TORCH_CHECK(d >= 1 && d <= (int64_t(1) << 15), "divisor out of range");
+  return (int64_t)avk::radix_recip((unsigned)d);
+}
+
 void pair_histogram(const at::Tensor& codes, int64_t n, const c10::optional<at::Tensor>& labels,
                     const at::Tensor& bins, const at::Tensor& pairs, const at::Tensor& poff,
                     int64_t max_tab, int64_t n_classes, at::Tensor& out) {
@@ -4219,6 +4224,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("radix_shape", &radix_shape);
   m.def("pack_radix", &pack_radix);
   m.def("class_histogram_radix", &class_histogram_radix);
+  m.def("radix_recip", &radix_recip);
   m.def("bigram_histogram", &bigram_histogram);
   m.def("class_moments", &class_moments);
   m.def("nb_predict", &nb_predict);

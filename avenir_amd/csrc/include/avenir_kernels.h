@@ -338,6 +338,8 @@ void pack_radix(const uint16_t* words, long long n, int B, const int* h_shift, c
 void class_histogram_radix(const uint32_t* dense, long long n, int B, const int* h_radix, const int* h_bins,
                            const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
                            int count_labels, unsigned long long* out, hipStream_t stream);
+// multiply-high reciprocal floor(2^32 / d) + 1 the radix kernel divides cell indices with (0 for d < 2)
+unsigned radix_recip(unsigned d);
 // K1 device CSV parse (csv.hip)
 long long csv_chunks(long long size);
 // tokens parsed since the last call whose rounding the device could not settle (then re-parse on the

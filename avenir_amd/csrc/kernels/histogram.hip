@@ -783,7 +783,16 @@ struct RadixSpec {
   int bins[8];  // digits >= bins[k] (the missing digit) are not counted
   int offs[8];  // first output column of feature k
   int crad;     // class radix: 1 = no class digit (C = 1), 2, or 3 when unknown labels occur (digit 2)
+  // cell decode without integer division: digit k of cell j is (j / stride[k]) % rad[k], both divisions
+  // as multiply-high by radix_recip of the divisor (div_small)
+  unsigned stride[8], srcp[8], rrcp[8], crcp;
 };
+
+// n / d for n < 2^15 and d <= 2^15 as the high word of n * m, m = floor(2^32 / d) + 1 (radix_recip):
+// exact because n d < 2^32; d = 1 has no 32-bit reciprocal and divides by nothing
+__device__ __forceinline__ unsigned div_small(unsigned n, unsigned d, unsigned m) {
+  return d == 1u ? n : __umulhi(n, m);
+}
 
 // 16-bit words of pack_rows -> dense B-bit stream of mixed-radix codes (container as pack_dense).
 // Every digit is clamped to its radix, so a code is < J whatever the words hold.
@@ -830,8 +839,10 @@ __global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restri
 // single shift-add as the cell address.  Epilogue: S = min(R, 8) lanes share a cell's R replicas
 // (item i = cell * S + part reads replica (i + S q) % R in round q: for R = 32 a 32-lane group
 // touches 32 different banks; with S = 1 this is the rotation (cell + q) % R), a cell's parts are
-// summed across its S lanes, the cell index is decoded digit by digit and added into the [C][TB]
-// table, and that table is flushed with one global atomic per non-zero entry.
+// summed across its S lanes (every lane of the cell then holds the count), the S lanes take the
+// cell's digits in turn (lane `part`: digits part, part + S, ...; the class-count column counts as
+// digit F) and add the count into the [C][TB] table, and that table is flushed with one global
+// atomic per non-zero entry.
 template <int B>
 __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* __restrict__ dense, long long n,
                                                                 RadixSpec rs, int J, int log2r, int nfeat,
@@ -841,20 +852,25 @@ __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* 
   constexpr unsigned M = (1u << B) - 1u;
   const int NT = (int)blockDim.x;
   const int R = 1 << log2r;
+  const int ctb = n_classes * total_bins;
   unsigned int* s_small = s_joint + ((size_t)J << log2r);
-  for (int i = threadIdx.x; i < (J << log2r) + n_classes * total_bins; i += NT) s_joint[i] = 0;
+  const long long groups = (n + 31) >> 5;
+  const long long stride = (long long)gridDim.x * NT;
+  uint32_t d[B + 1];
+  d[B] = 0;
+  auto load = [&](long long g) __attribute__((always_inline)) {
+    const uint32_t* src = dense + g * B;
+#pragma unroll
+    for (int i = 0; i < B; ++i) d[i] = src[i];
+  };
+  long long g = (long long)blockIdx.x * NT + threadIdx.x;
+  if (g < groups) load(g);  // the first group is in flight while the tables are cleared
+  for (int i = threadIdx.x; i < (J << log2r) + ctb; i += NT) s_joint[i] = 0;
   // byte address of a record's counter = lane base + (code << (log2 R + 2)): one v_lshl_add_u32
   char* const my = reinterpret_cast<char*>(s_joint + (threadIdx.x & (unsigned)(R - 1)));
   const unsigned lr = (unsigned)log2r + 2u;
   __syncthreads();
-  const long long groups = (n + 31) >> 5;
-  const long long stride = (long long)gridDim.x * NT;
-  for (long long g = (long long)blockIdx.x * NT + threadIdx.x; g < groups; g += stride) {
-    uint32_t d[B + 1];
-    const uint32_t* src = dense + g * B;
-#pragma unroll
-    for (int i = 0; i < B; ++i) d[i] = src[i];
-    d[B] = 0;
+  while (g < groups) {
     const long long left = n - (g << 5);
     auto rec = [&](int k) __attribute__((always_inline)) -> unsigned {
       const int bit = k * B, i = bit >> 5, sh = bit & 31;
@@ -869,6 +885,8 @@ __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* 
       for (int k = 0; k < 32; ++k)
         if (k < left) atomicAdd(reinterpret_cast<unsigned int*>(my + (rec(k) << lr)), 1u);
     }
+    g += stride;
+    if (g < groups) load(g);
   }
   __syncthreads();
   const int ls = log2r < 3 ? log2r : 3;  // S = 2^ls lanes per cell
@@ -876,31 +894,28 @@ __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* 
   const int items = J << ls;
   for (int base = 0; base < items; base += NT) {  // block-uniform bound: every lane takes part in the shuffles
     const int i = base + (int)threadIdx.x;
-    const int cell = i >> ls;
+    const unsigned cell = (unsigned)(i >> ls);
     unsigned cnt = 0;
     if (i < items)
       for (int q = 0; q < (R >> ls); ++q) cnt += s_joint[((size_t)cell << log2r) + ((i + (q << ls)) & (R - 1))];
     for (int o = S >> 1; o; o >>= 1) cnt += __shfl_xor(cnt, o);
-    unsigned j = (unsigned)cell;
-    int c = 0;
-    if (rs.crad > 1) {
-      c = (int)(j % (unsigned)rs.crad);
-      j /= (unsigned)rs.crad;
-    }
-    // the first lane of a cell holds its count; an unknown class is not counted (as in the column histogram)
-    if (i < items && !(i & (S - 1)) && cnt && c < n_classes) {
+    const unsigned c = cell - div_small(cell, (unsigned)rs.crad, rs.crcp) * (unsigned)rs.crad;  // crad = 1: class 0
+    // an unknown class is not counted (as in the column histogram)
+    if (i < items && cnt && c < (unsigned)n_classes) {
       unsigned int* row = s_small + c * total_bins;
-      for (int kf = 0; kf < nfeat; ++kf) {
-        const unsigned rk = (unsigned)rs.rad[kf];
-        const int code = (int)(j % rk);
-        j /= rk;
-        if (code < rs.bins[kf]) atomicAdd(&row[rs.offs[kf] + code], cnt);
+      for (int kf = i & (S - 1); kf <= nfeat; kf += S) {
+        if (kf == nfeat) {
+          if (count_labels) atomicAdd(&row[total_bins - 1], cnt);
+          break;
+        }
+        const unsigned q = div_small(cell, rs.stride[kf], rs.srcp[kf]), rk = (unsigned)rs.rad[kf];
+        const unsigned code = q - div_small(q, rk, rs.rrcp[kf]) * rk;
+        if (code < (unsigned)rs.bins[kf]) atomicAdd(&row[rs.offs[kf] + code], cnt);
       }
-      if (count_labels) atomicAdd(&row[total_bins - 1], cnt);
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < n_classes * total_bins; i += NT) {
+  for (int i = threadIdx.x; i < ctb; i += NT) {
     const unsigned cnt = s_small[i];
     if (cnt) atomicAdd(&out[i], (unsigned long long)cnt);
   }
@@ -1360,6 +1375,9 @@ void class_histogram_dense(const uint32_t* dense, long long n, int B, const int*
 // ---- mixed-radix records ----
 constexpr int kLdsPerCu = 160 * 1024;
 
+// multiply-high reciprocal of a divisor 2 <= d <= 2^15 (div_small); 0 for d = 1, which has none
+unsigned radix_recip(unsigned d) { return d < 2u ? 0u : (unsigned)((1ull << 32) / d + 1ull); }
+
 // J = product of the radices; throws on anything the kernels could not index safely
 static RadixSpec radix_spec(const int* h_radix, const int* h_bins, const int* h_offs, int nfeat, int class_radix,
                             int n_classes, int total_bins, long long* J) {
@@ -1369,6 +1387,7 @@ static RadixSpec radix_spec(const int* h_radix, const int* h_bins, const int* h_
     throw std::runtime_error("radix histogram: class radix 1 (C = 1), 2 or 3 (C = 2)");
   RadixSpec rs{};
   rs.crad = class_radix;
+  rs.crcp = radix_recip((unsigned)class_radix);
   long long j = class_radix;
   for (int k = 0; k < nfeat; ++k) {
     if (h_bins[k] < 1 || (h_radix[k] != h_bins[k] && h_radix[k] != h_bins[k] + 1))
@@ -1378,6 +1397,9 @@ static RadixSpec radix_spec(const int* h_radix, const int* h_bins, const int* h_
     rs.rad[k] = h_radix[k];
     rs.bins[k] = h_bins[k];
     rs.offs[k] = h_offs[k];
+    rs.stride[k] = (unsigned)j;
+    rs.srcp[k] = radix_recip((unsigned)j);
+    rs.rrcp[k] = radix_recip((unsigned)h_radix[k]);
     j *= h_radix[k];
     if (j > (1LL << 15)) throw std::runtime_error("radix histogram: more than 2^15 joint states");
   }
