@@ -1,3 +1,4 @@
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <condition_variable>
@@ -2084,6 +2085,102 @@ at::Tensor kmeans_update(const at::Tensor& flat, at::Tensor& C2, at::Tensor& Cn,
   avk::kmeans_update(flat.data_ptr<double>(), (int)K, (int)D, (int)R, run_of.data_ptr<int>(), frozen.data_ptr<uint8_t>(),
                      C2.data_ptr<float>(), Cn.data_ptr<float>(), moves.data_ptr<float>(), cur_stream(C2));
   return moves;
+}
+
+// Many independent k-means fits in one call (kmeans_groups.hip): X [N, Dp] holds the groups' rows
+// concatenated (D zero-padded to Dp), groups [G, 2] (row offset, rows) and runs [R, 3] (group, k,
+// centroid offset) are HOST int64 tables, C0 [Ktot, Dp] the initial centroids, thr [R] the host
+// fp64 convergence thresholds (tol^2, or tol_eff in sklearn mode = 1).  Every table entry is
+// checked here, then the runs go out by descending group size, one launch per workgroup-size class.
+// -> (centroids [Ktot, Dp], counts int32 [Ktot], sse f64 [R], iterations int32 [R], converged
+// int32 [R], SSE history f64 [R, max_iter], status int32 [G]: 1 = non-finite data, group skipped)
+std::vector<at::Tensor> kmeans_fit_groups(const at::Tensor& X, const at::Tensor& groups, const at::Tensor& runs,
+                                          const at::Tensor& C0, const at::Tensor& thr, int64_t D, int64_t max_iter,
+                                          int64_t mode) {
+  CHECK_DEV(X);
+  CHECK_DTYPE(X, at::kFloat);
+  CHECK_DEV(C0);
+  CHECK_DTYPE(C0, at::kFloat);
+  TORCH_CHECK(C0.device() == X.device(), "C0 must be on X's device");
+  TORCH_CHECK(X.dim() == 2 && C0.dim() == 2, "X must be [N, Dp] and C0 [Ktot, Dp]");
+  const int64_t N = X.size(0), DP = X.size(1), KT = C0.size(0);
+  TORCH_CHECK(DP == 2 || DP == 4 || DP == 8 || DP == 16 || DP == 32 || DP == 64,
+              "D must be padded to 2/4/8/16/32/64 (D <= 64)");
+  TORCH_CHECK(D >= 1 && D <= DP && C0.size(1) == DP, "1 <= D <= Dp, and C0 as wide as X");
+  TORCH_CHECK(aligned(X, 16) && aligned(C0, 16), "X and C0 must be 16-byte aligned");
+  TORCH_CHECK(max_iter >= 0 && max_iter <= (1 << 20), "0 <= max_iter <= 2^20");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode: 0 = shift, 1 = sklearn");
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&groups, &runs}) {
+    TORCH_CHECK(t->device().is_cpu() && t->scalar_type() == at::kLong && t->is_contiguous() && t->dim() == 2,
+                "groups / runs must be contiguous host int64 tables");
+  }
+  TORCH_CHECK(groups.size(1) == 2 && runs.size(1) == 3, "groups [G, 2], runs [R, 3]");
+  const int64_t G = groups.size(0), R = runs.size(0);
+  TORCH_CHECK(thr.device().is_cpu() && thr.scalar_type() == at::kDouble && thr.is_contiguous() && thr.numel() == R,
+              "thr must be a host fp64 [R]");
+  TORCH_CHECK(R >= 1 && R < (1LL << 31) && G >= 1, "at least one group and one run");
+  TORCH_CHECK(R * std::max<int64_t>(max_iter, 1) < (1LL << 31), "SSE history exceeds 2^31 entries");
+  const int64_t* gp = groups.data_ptr<int64_t>();
+  const int64_t* rp = runs.data_ptr<int64_t>();
+  const double* tp = thr.data_ptr<double>();
+  for (int64_t g = 0; g < G; ++g) {
+    TORCH_CHECK(gp[2 * g + 1] >= 1 && gp[2 * g + 1] <= (1LL << 22), "rows per group must be in [1, 2^22]");
+    TORCH_CHECK(gp[2 * g] >= 0 && gp[2 * g] <= N - gp[2 * g + 1], "group ", g, " lies outside X");
+  }
+  struct Rec { int64_t n, r; int threads; };
+  std::vector<Rec> order((size_t)R);
+  std::vector<uint8_t> owned((size_t)KT, 0);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t g = rp[3 * r], k = rp[3 * r + 1], co = rp[3 * r + 2];
+    TORCH_CHECK(g >= 0 && g < G, "run ", r, " points past the group table");
+    TORCH_CHECK(k >= 1 && k <= 64, "k must be in [1, 64]");
+    TORCH_CHECK(co >= 0 && co <= KT - k, "run ", r, " points past the centroid table");
+    for (int64_t c = co; c < co + k; ++c) {
+      TORCH_CHECK(!owned[(size_t)c], "runs must not share centroid rows");
+      owned[(size_t)c] = 1;
+    }
+    TORCH_CHECK(tp[r] == tp[r], "thr must not be NaN");
+    order[(size_t)r] = {gp[2 * g + 1], r, avk::kmeans_groups_threads(gp[2 * g + 1])};
+  }
+  std::stable_sort(order.begin(), order.end(), [](const Rec& a, const Rec& b) { return a.n > b.n; });
+  auto tab = at::empty({R, 8}, at::TensorOptions().dtype(at::kLong).pinned_memory(false));
+  int64_t* tb = tab.data_ptr<int64_t>();
+  struct Launch { int64_t first, count; int threads; size_t lds; };
+  std::vector<Launch> launches;
+  for (int64_t i = 0; i < R; ++i) {
+    const int64_t r = order[(size_t)i].r, g = rp[3 * r], k = rp[3 * r + 1];
+    const int rep = avk::kmeans_groups_rep((int)k, (int)DP);
+    int64_t* o = tb + 8 * i;
+    o[0] = gp[2 * g];
+    o[1] = gp[2 * g + 1];
+    o[2] = k;
+    o[3] = rp[3 * r + 2];
+    o[4] = g;
+    o[5] = r;
+    std::memcpy(&o[6], &tp[r], sizeof(double));
+    o[7] = rep;
+    const size_t lds = avk::kmeans_groups_lds((int)k, (int)DP, rep);
+    if (launches.empty() || launches.back().threads != order[(size_t)i].threads)
+      launches.push_back({i, 0, order[(size_t)i].threads, 0});
+    launches.back().count++;
+    launches.back().lds = std::max(launches.back().lds, lds);
+  }
+  DevGuard guard(X.device());
+  auto dtab = tab.to(X.device());
+  auto C = C0.clone();
+  auto iopt = X.options().dtype(at::kInt), dopt = X.options().dtype(at::kDouble);
+  auto counts = at::zeros({KT}, iopt);
+  auto sse = at::zeros({R}, dopt);
+  auto iters = at::zeros({R}, iopt);
+  auto conv = at::zeros({R}, iopt);
+  auto hist = at::zeros({R, max_iter}, dopt);
+  auto status = at::zeros({G}, iopt);
+  for (const Launch& l : launches)
+    avk::kmeans_groups(X.data_ptr<float>(), reinterpret_cast<const long long*>(dtab.data_ptr<int64_t>()) + 8 * l.first, (int)l.count, (int)DP, (int)D,
+                       l.threads, l.lds, (int)max_iter, (int)mode, C.data_ptr<float>(), counts.data_ptr<int>(),
+                       sse.data_ptr<double>(), iters.data_ptr<int>(), conv.data_ptr<int>(), hist.data_ptr<double>(),
+                       status.data_ptr<int>(), cur_stream(X));
+  return {C, counts, sse, iters, conv, hist, status};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4324,6 +4421,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("kmeans_assign", &kmeans_assign);
   m.def("kmeans_reduce", &kmeans_reduce);
   m.def("kmeans_update", &kmeans_update);
+  m.def("kmeans_fit_groups", &kmeans_fit_groups);
   m.def("ngram_count", &ngram_count);
   m.def("uniformization", &uniformization);
   m.def("dot_matrix", &dot_matrix);

@@ -265,6 +265,16 @@ void kmeans_reduce(const float* partial, const double* sse_partial, int grid, in
 void kmeans_update(const double* flat, int K, int D, int R, const int* run_of, const unsigned char* frozen, float* C2,
                    float* Cn, float* moves, hipStream_t stream);
 
+// ---- kmeans_groups.hip (K16g) --------------------------------------------------------------
+// one workgroup per (group, k, restart) run, the whole Lloyd loop on the device.  tab: nruns
+// records of 8 int64 (row offset, rows, k, centroid offset, group, run id, threshold bits, replicas)
+int kmeans_groups_threads(long long n);
+int kmeans_groups_rep(int k, int DP);
+size_t kmeans_groups_lds(int k, int DP, int rep);
+void kmeans_groups(const float* X, const long long* tab, int nruns, int DP, int D, int threads, size_t lds,
+                   int max_iter, int mode, float* C, int* counts, double* sse, int* iters, int* conv, double* hist,
+                   int* status, hipStream_t stream);
+
 // seqmine.hip (K5 n-gram hash counts, K16 uniformisation, K19 dot-matrix matching)
 void ngram_count(const short* st, long long n, int L, int S, int min_len, int max_len, const int* group,
                  unsigned long long group_mul, unsigned long long* keys, unsigned* counts, unsigned long long cap,

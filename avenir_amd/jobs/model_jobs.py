@@ -146,14 +146,18 @@ def kmeanspp(args):
     models = [KMeans([c for c in ks if c <= X.shape[0]], n_init=ctx.get_int("num.clustGroup", 10),
                      max_iter=ctx.get_int("num.iter", 10), init="k-means++", comm=local) for X in Xs]
     inits = KMeans.init_many(models, Xs)        # every group's seeding in one batched pass
-    for (k, _), X, km, C0 in zip(groups, Xs, models, inits):
+    KMeans.fit_many(models, Xs, inits)          # every group's Lloyd loops in one launch (GPU)
+    best = [km.best[c] for km in models for c in km.ks]
+    rows = torch.cat([r.centroids for r in best]).cpu().tolist() if best else []   # one device read
+    o = 0
+    for (k, _), km in zip(groups, models):
         kk = km.ks
-        km.fit(X, init_centroids=C0)
         for c in kk:
             run = km.best[c]
             out.append(d.join(list(k) + [str(c), fmt(run.sse, prec)]))
             cents += [d.join(list(k) + [str(c), str(i)] + [fmt(v, prec) for v in cc])
-                      for i, cc in enumerate(run.centroids.cpu().tolist())]
+                      for i, cc in enumerate(rows[o:o + c])]
+            o += c
         if len(kk) > 2:
             out.append(d.join(list(k) + ["knuckle", str(km.knuckle_k())]))
     ctx.emit(out)

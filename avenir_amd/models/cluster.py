@@ -12,6 +12,9 @@ MI355X: a group of up to 16 runs shares ONE pass over the data per iteration (K1
 scoring against SGPR-resident centroid pairs, one-hot x rows on the matrix cores for the partial
 sums), a deterministic device reduction, ONE all-reduce of the flat [K (D+1) + R] statistics
 replaces the shuffle, and the centroid update + movement test run on the device.
+Many small-to-medium fits (one model per key group: kMeansPlusPlusCluster) go through
+``KMeans.fit_many`` instead: every (model, k, restart) run is one workgroup of ONE launch that
+iterates to convergence on the device (``models/kmeans_groups.py``, ``kmeans_groups.hip``).
 """
 from __future__ import annotations
 
@@ -325,6 +328,71 @@ class KMeans:
             if r.k not in self.best or r.sse < self.best[r.k].sse:
                 self.best[r.k] = r
         return self
+
+    # One workgroup per run is the wrong shape for a very large group, where K16 streams at HBM
+    # rate: models with more rows, or more padded values, than this keep the per-model fit.  Measured
+    # on ONE group (9 runs: the batched path's worst case, 9 workgroups on 256 CUs), fit_many against
+    # fit: D = 2 wins up to 2^17 rows (1.5x) and ties at 2^18; D = 16 wins up to 2^15 rows (1.9x) and
+    # loses at 2^16 (0.7x): profiles/kmeans_groups_cap_sweep.jsonl
+    GROUPS_MAX_ROWS = 1 << 17
+    GROUPS_MAX_VALUES = 1 << 19      # rows x D padded to 2/4/8/16/32/64
+
+    @staticmethod
+    def fit_many(models: list["KMeans"], Xs: list[torch.Tensor],
+                 init_centroids: list[list[torch.Tensor]] | None = None,
+                 use_kernel: bool | None = None) -> list["KMeans"]:
+        """Fit model i on ``Xs[i]``: every (model, k, restart) run of the call in ONE launch of the
+        device Lloyd loops (models/kmeans_groups.py: one workgroup per run, no host round trip per
+        iteration), instead of one ``fit`` per model.  Missing ``init_centroids`` come from
+        :meth:`init_many`.  A model takes the batched path when it is not distributed, has no
+        ``recovery``, D <= 64, every k <= 64, at most ``GROUPS_MAX_ROWS`` rows and
+        ``GROUPS_MAX_VALUES`` padded values, and either
+        ``use_kernel`` is True or it is None with ``X`` on CUDA and the extension loaded; every other
+        model goes through ``fit(X, init_centroids=...)`` as before — so on the CPU the default is
+        the per-model fit with unchanged results, and the host twin runs only with
+        ``use_kernel=True``.  ``AVMI_KMEANS_GROUPS=0`` forces the per-model path (A/B runs).  The
+        batched path scores with direct differences and does not translate the data."""
+        import os
+        from . import kmeans_groups as kg
+        Xs = [X.float().contiguous() for X in Xs]
+        if init_centroids is None:
+            init_centroids = KMeans.init_many(models, Xs)
+        off = os.environ.get("AVMI_KMEANS_GROUPS", "1") == "0"
+        batches: dict[tuple, list[int]] = {}
+        for i, (km, X) in enumerate(zip(models, Xs)):
+            comm = km.comm or get_comm()
+            specs = km.run_specs()
+            ok = (not off and use_kernel is not False and specs and not comm.is_distributed
+                  and km.recovery is None and 1 <= X.shape[1] <= kg.MAX_D and max(km.ks) <= kg.MAX_K
+                  and 1 <= X.shape[0] <= min(KMeans.GROUPS_MAX_ROWS, kg.MAX_ROWS)
+                  and X.shape[0] * kg.padded_dim(X.shape[1]) <= KMeans.GROUPS_MAX_VALUES
+                  and (use_kernel is True or (X.is_cuda and _native.available())))
+            if ok:
+                batches.setdefault((X.device, X.shape[1], km.max_iter, km.tol, km.tol_mode), []).append(i)
+            else:
+                km.fit(X, init_centroids=init_centroids[i])
+        for (dev, _, max_iter, tol, tol_mode), idx in batches.items():
+            run_group, inits, effs = [], [], []
+            for j, i in enumerate(idx):
+                km = models[i]
+                _, km._tol_eff = km._feature_stats(Xs[i], km.comm or get_comm(), want_mean=False)
+                for C in init_centroids[i]:
+                    run_group.append(j)
+                    inits.append(C.float())
+                    effs.append(km._tol_eff)
+            res = kg.kmeans_fit_groups([Xs[i] for i in idx], run_group, inits, max_iter, tol, tol_mode,
+                                       effs if tol_mode == "sklearn" else None, dev)
+            o = 0
+            for i in idx:
+                km = models[i]
+                km.runs, km.best, km._shift = [], {}, None
+                for (k, sd), g in zip(km.run_specs(), res[o:o + len(init_centroids[i])]):
+                    r = KMeansRun(k, sd, g.centroids, g.sse, g.iterations, g.counts, g.converged, g.history)
+                    km.runs.append(r)
+                    if k not in km.best or r.sse < km.best[k].sse:
+                        km.best[k] = r
+                o += len(init_centroids[i])
+        return models
 
     def _feature_stats(self, X: torch.Tensor, comm, want_mean: bool):
         """(global per-feature mean f64 [D] or None, effective tolerance) from ONE all-reduce of the
