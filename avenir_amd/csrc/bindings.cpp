@@ -1568,6 +1568,73 @@ void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tenso
                   (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(pop));
 }
 
+// feature subsets scored by naive Bayes (optim.hip::subset_errors_kernel, ga_subset_kernel): the
+// checks shared by both bindings.  Labels are only compared, so any int32 is in range.
+static void subset_check(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tensor& labels, const char* who) {
+  CHECK_DEV(LL);
+  CHECK_DTYPE(LL, at::kFloat);
+  TORCH_CHECK(LL.dim() == 3 && LL.is_contiguous(), who, ": LL must be contiguous [N, F, C]");
+  const int64_t N = LL.size(0), F = LL.size(1), C = LL.size(2);
+  TORCH_CHECK(F >= 1 && F <= 32 && C >= 2 && C <= 16, who, ": 1 <= F <= 32 and 2 <= C <= 16");
+  TORCH_CHECK(N >= 1 && N < (1LL << 24), who, ": 1 <= N < 2^24 rows");
+  CHECK_DEV(log_prior);
+  CHECK_DTYPE(log_prior, at::kFloat);
+  TORCH_CHECK(log_prior.dim() == 1 && log_prior.numel() == C && log_prior.is_contiguous(), who, ": log_prior must be [C]");
+  CHECK_DEV(labels);
+  CHECK_DTYPE(labels, at::kInt);
+  TORCH_CHECK(labels.dim() == 1 && labels.numel() == N && labels.is_contiguous(), who, ": labels must be int32 [N]");
+  TORCH_CHECK(log_prior.device() == LL.device() && labels.device() == LL.device(), who, ": tensors on one device");
+}
+
+// masks int32 [B] (bit f = feature f; bits at or above F are ignored) -> int32 [B] error counts
+at::Tensor subset_errors(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tensor& labels,
+                         const at::Tensor& masks) {
+  subset_check(LL, log_prior, labels, "subset_errors");
+  CHECK_DEV(masks);
+  CHECK_DTYPE(masks, at::kInt);
+  TORCH_CHECK(masks.dim() == 1 && masks.is_contiguous() && masks.device() == LL.device(),
+              "subset_errors: masks must be contiguous int32 [B] on the device of LL");
+  TORCH_CHECK(masks.numel() <= (1LL << 30), "subset_errors: at most 2^30 masks");
+  DevGuard g(LL.device());
+  at::Tensor out = at::empty({masks.numel()}, masks.options());
+  avk::subset_errors(LL.data_ptr<float>(), log_prior.data_ptr<float>(), labels.data_ptr<int>(), (int)LL.size(0),
+                     (int)LL.size(1), (int)LL.size(2), reinterpret_cast<const unsigned*>(masks.data_ptr<int>()),
+                     (int)masks.numel(), out.data_ptr<int>(), cur_stream(LL));
+  return out;
+}
+
+void ga_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tensor& labels, int64_t min_size,
+               int64_t max_size, double invalid, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& hist, int64_t G,
+               int64_t m, int64_t r, bool purge_first, bool mutate, int64_t seed, int64_t island_base,
+               int64_t gen_base) {
+  subset_check(LL, log_prior, labels, "ga_subset");
+  const int64_t N = LL.size(0), F = LL.size(1), C = LL.size(2);
+  TORCH_CHECK(min_size >= 0 && min_size <= max_size && max_size <= 32, "ga_subset: 0 <= min_size <= max_size <= 32");
+  TORCH_CHECK(G >= 0 && gen_base >= 0 && gen_base + G < (1LL << 40), "generation counter out of range");
+  CHECK_DEV(pop);
+  CHECK_DTYPE(pop, at::kShort);
+  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == F && pop.is_contiguous(), "pop must be contiguous [islands, P, F]");
+  const int64_t I = pop.size(0), P = pop.size(1);
+  TORCH_CHECK(I < (1LL << 31), "ga_subset: too many islands");
+  TORCH_CHECK(P >= 2 && P <= 64 && r >= 1 && r <= std::min<int64_t>(P, 32) && m >= 1 && m <= P,
+              "ga_subset: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
+  TORCH_CHECK(purge_first || P + r <= 64, "ga_subset: P + r <= 64 when children join the pool");
+  TORCH_CHECK(avk::ga_subset_lds((int)N, (int)F, (int)C) <= 48 * 1024, "ga_subset: more than 48 KiB of tile LDS");
+  CHECK_DEV(pop_cost);
+  CHECK_DTYPE(pop_cost, at::kFloat);
+  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, "pop_cost must be [islands, P]");
+  CHECK_DEV(hist);
+  CHECK_DTYPE(hist, at::kFloat);
+  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, "hist must be [islands, G]");
+  TORCH_CHECK(pop.device() == LL.device() && pop_cost.device() == LL.device() && hist.device() == LL.device(),
+              "ga_subset: tensors on one device");
+  DevGuard g(LL.device());
+  avk::ga_subset(LL.data_ptr<float>(), log_prior.data_ptr<float>(), labels.data_ptr<int>(), (int)N, (int)F, (int)C,
+                 (int)min_size, (int)max_size, (float)invalid, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(),
+                 hist.data_ptr<float>(), (int)I, (int)P, (int)G, (int)m, (int)r, purge_first ? 1 : 0, mutate ? 1 : 0,
+                 (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(LL));
+}
+
 // ---------------------------------------------------------------------------------------------
 // generalised linear models (K13)
 // ---------------------------------------------------------------------------------------------
@@ -4393,6 +4460,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("ga_assign_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_assign_lds((int)P, (int)L, (int)r); });
   m.def("ga_meeting", &ga_meeting);
   m.def("ga_meeting_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_meeting_lds((int)P, (int)L, (int)r); });
+  m.def("subset_errors", &subset_errors);
+  m.def("ga_subset", &ga_subset);
+  m.def("ga_subset_lds", [](int64_t N, int64_t F, int64_t C) { return (int64_t)avk::ga_subset_lds((int)N, (int)F, (int)C); });
   m.def("smote_lines", &smote_lines);
   m.def("format_device", &format_device);
   m.def("pairs_within", &pairs_within);

@@ -138,6 +138,18 @@ size_t ga_meeting_lds(int P, int L, int r);
 void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* pop_cost, float* hist, int islands,
                 int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
                 long long island_base, unsigned long long gen_base, hipStream_t stream);
+// feature subsets scored by naive Bayes: LL [N][F][C] log-likelihoods, log_prior [C], labels [N];
+// a subset is a 32-bit mask (bit f = feature f).  subset_errors clears out [B] and writes the
+// number of mis-predicted rows of each mask; ga_subset is the island GA over such masks with
+// min_size <= popcount <= max_size, pop [islands][P][F] of 0 / 1 (packed inside the kernel)
+int ga_subset_threads(int N);              // workgroup size of ga_subset
+size_t ga_subset_lds(int N, int F, int C);  // bytes of dynamic LDS (the row tile) per island
+void subset_errors(const float* LL, const float* log_prior, const int* labels, int N, int F, int C,
+                   const unsigned* masks, int B, int* out, hipStream_t stream);
+void ga_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, float invalid, short* pop, float* pop_cost, float* hist, int islands, int P, int G, int m,
+               int r, int purge_first, int mutate, unsigned long long seed, long long island_base,
+               unsigned long long gen_base, hipStream_t stream);
 void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
                short* best_sol, float* best_cost, int P, int iters, float t0, float cool, int interval,
                int geometric, int max_retry, unsigned long long seed, unsigned long long offset,

@@ -8,7 +8,9 @@
 // [L][V] cost table and an [L][L] conflict table, and every lane runs one chain for `iters`
 // Metropolis steps: O(1) cost delta per move, O(L) validity check, Philox randomness, geometric or
 // linear cooling — the whole optimisation is one kernel launch for thousands of chains.
+#include <algorithm>
 #include <stdexcept>
+#include <string>
 
 #include "avenir_common.h"
 #include "avenir_kernels.h"
@@ -153,11 +155,13 @@ __device__ __forceinline__ void ga_rank(const float* c, int n, int lane, int* or
   }
 }
 
-// Step 4 of a generation (both island kernels; every lane of the workgroup calls it): the source
-// of every next-pool slot -> nsrc, then the next pool pb / pc2 gathered from pa / kid.
-__device__ __forceinline__ void ga_replace(const short* pa, short* pb, const short* kid, const float* pc, float* pc2,
+// Step 4 of a generation (every island kernel; every thread of the workgroup calls it, `nt` of them):
+// the source of every next-pool slot -> nsrc, then the next pool pb / pc2 gathered from pa / kid.
+// A solution is L elements of T (L shorts, or one 32-bit mask).
+template <class T>
+__device__ __forceinline__ void ga_replace(const T* pa, T* pb, const T* kid, const float* pc, float* pc2,
                                            const float* kc, const int* ord, const int* kord, int* nsrc, int P, int L,
-                                           int r, int purge_first, int lane) {
+                                           int r, int purge_first, int lane, int nt = 64) {
   if (purge_first) {
     if (lane < P) nsrc[lane] = lane < P - r ? ord[lane] : P + kord[lane - (P - r)];
   } else if (lane < P + r) {
@@ -174,7 +178,7 @@ __device__ __forceinline__ void ga_replace(const short* pa, short* pb, const sho
     if (rk < P) nsrc[rk] = src;
   }
   __syncthreads();
-  for (int e = lane; e < P * L; e += 64) {
+  for (int e = lane; e < P * L; e += nt) {
     const int slot = e / L, l = e - slot * L;
     const int src = nsrc[slot];
     pb[e] = src < P ? pa[(size_t)src * L + l] : kid[(size_t)(src - P) * L + l];
@@ -482,6 +486,287 @@ __global__ __launch_bounds__(64) void ga_meeting_kernel(
   if (lane < P) pop_cost[isl * P + lane] = pc[lane];
 }
 
+// ---- feature subsets scored by naive Bayes (P/app/fesel.py, optimize/domains.py) ---------------
+// LL [N][F][C] holds per-row, per-feature, per-class log-likelihoods; a subset is a 32-bit mask
+// (bit f = feature f included).  The score of row n and class c is log_prior[c] plus LL[n][f][c]
+// over the set bits, f ascending, one fp32 add each; the prediction is the lowest c with the
+// largest score and a subset's error count is the number of rows whose prediction differs from
+// the label.  Counts are integers, so they depend on no grid, tile or workgroup size.
+//
+// Both kernels stage a tile of TR rows in LDS (row stride F C | 1: lanes on consecutive rows hit
+// distinct banks) and give every thread one row of the tile.  With TR >= 64 a wave shares its
+// masks: each is read by broadcast into a scalar register, the scalar unit walks its set bits and
+// one ballot count per mask goes to the LDS counters.  Tiles of 16 or 32 rows (F C > 191) put
+// several masks on a wave: every thread then takes groups of FS_K masks, reads each LL value once
+// per group and applies it to FS_K running scores under the masks' bits.
+// optimize/ga_subset.py holds the bit-exact host twins.
+constexpr int FS_TILE_BYTES = 48 * 1024, FS_MASK_CHUNK = 1024, FS_K = 4, FS_MAX_C = 16;
+
+inline int fs_tile_rows(int FC, int nt) {
+  int tr = nt;
+  while (tr > 16 && (size_t)tr * (FC | 1) * sizeof(float) > (size_t)FS_TILE_BYTES) tr >>= 1;
+  return tr;
+}
+
+// rows [n0, n0 + nr) of LL -> tile; magic = ceil(2^32 / FC) turns e / FC into one multiply
+// (exact while e FC < 2^32; e < 2^14 and FC <= 512 here)
+__device__ __forceinline__ void fs_stage(float* tile, const float* __restrict__ LL, long long n0, int nr, int FC,
+                                         int stride, unsigned magic, int tid, int nt) {
+  const float* src = LL + n0 * FC;
+  const int tot = nr * FC;
+  for (int e = tid; e < tot; e += nt) {
+    const int row = (int)__umulhi((unsigned)e, magic);
+    tile[row * stride + (e - row * FC)] = src[e];
+  }
+}
+
+// The scoring core: is the row with log-likelihoods ll [F][C] mis-predicted under each of K subsets?
+template <int K>
+__device__ __forceinline__ void fs_row_miss(const float* ll, const float* prior, int F, int C, const unsigned (&mk)[K],
+                                            int label, bool (&miss)[K]) {
+  float best[K];
+  int bc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    best[k] = 0.f;
+    bc[k] = 0;
+  }
+  for (int c = 0; c < C; ++c) {
+    float s[K];
+    const float p = prior[c];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = p;
+    const float* q = ll + c;
+    for (int f = 0; f < F; ++f) {
+      const float v = q[f * C];
+#pragma unroll
+      for (int k = 0; k < K; ++k) s[k] = ((mk[k] >> f) & 1u) ? s[k] + v : s[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (c == 0 || s[k] > best[k]) {
+        best[k] = s[k];
+        bc[k] = c;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) miss[k] = bc[k] != label;
+}
+
+// The same scores for ONE subset that the whole wave shares (mk in a scalar register): the scalar
+// unit walks the set bits, f ascending, and the vector unit spends one add per included feature
+// and class; two classes advance together for independent add chains.
+__device__ __forceinline__ bool fs_row_miss_uniform(const float* ll, const float* prior, int C, unsigned mk, int label) {
+  float best = 0.f;
+  int bc = 0;
+  for (int c = 0; c < C; c += 2) {
+    const bool two = c + 1 < C;
+    float s0 = prior[c], s1 = two ? prior[c + 1] : 0.f;
+    const float* q = ll + c;
+    for (unsigned m = mk; m; m &= m - 1u) {
+      const int o = (__ffs(m) - 1) * C;
+      s0 = s0 + q[o];
+      if (two) s1 = s1 + q[o + 1];
+    }
+    if (c == 0 || s0 > best) {
+      best = s0;
+      bc = c;
+    }
+    if (two && s1 > best) {
+      best = s1;
+      bc = c + 1;
+    }
+  }
+  return bc != label;
+}
+
+// Every thread of the workgroup: the nr staged rows against the masks masks[d], d = idx[j] (or j
+// without idx), j < nm; the misses of mask d are added to cnt[d].  labels points at the tile's row 0.
+__device__ __forceinline__ void fs_score_tile(const float* tile, int stride, int TR, int nr, const float* prior, int F,
+                                              int C, const int* __restrict__ labels, const unsigned* masks,
+                                              const int* idx, int nm, int* cnt, int tid, int nt) {
+  const int sh = __ffs(TR) - 1;  // TR and nt are powers of two, TR <= nt
+  const int row = tid & (TR - 1), slot = tid >> sh, nslot = nt >> sh;
+  const bool live = row < nr;
+  const int label = live ? labels[row] : 0;
+  const float* ll = tile + row * stride;
+  if (TR >= 64) {  // a wave shares slot, hence its masks: one ballot count per mask
+    for (int j = __builtin_amdgcn_readfirstlane(slot); j < nm; j += nslot) {
+      const int dst = idx ? idx[j] : j;
+      const unsigned mk = (unsigned)__builtin_amdgcn_readfirstlane((int)masks[dst]);
+      const bool hit = fs_row_miss_uniform(ll, prior, C, mk, label) && live;
+      const int n = __popcll(__ballot(hit));
+      if ((tid & 63) == 0 && n) atomicAdd(&cnt[dst], n);
+    }
+    return;
+  }
+  for (int j0 = slot * FS_K; j0 < nm; j0 += nslot * FS_K) {
+    unsigned mk[FS_K];
+    int dst[FS_K];
+#pragma unroll
+    for (int k = 0; k < FS_K; ++k) {
+      const int j = j0 + k;
+      dst[k] = j < nm ? (idx ? idx[j] : j) : -1;
+      mk[k] = dst[k] >= 0 ? masks[dst[k]] : 0u;
+    }
+    bool miss[FS_K];
+    fs_row_miss<FS_K>(ll, prior, F, C, mk, label, miss);
+#pragma unroll
+    for (int k = 0; k < FS_K; ++k) {
+      if (live && miss[k] && dst[k] >= 0) atomicAdd(&cnt[dst[k]], 1);
+    }
+  }
+}
+
+// out[b] += the error count of masks[b] over this block's row tiles (tiles blockIdx.x, + gridDim.x,
+// ...); the launcher clears out.  Masks go through LDS in chunks of mchunk <= FS_MASK_CHUNK, the
+// chunks dealt over blockIdx.y so that few row tiles still fill the chip.
+__global__ __launch_bounds__(256) void subset_errors_kernel(
+    const float* __restrict__ LL, const float* __restrict__ log_prior, const int* __restrict__ labels, int N, int F,
+    int C, const unsigned* __restrict__ masks, int B, int* __restrict__ out, int TR, int mchunk) {
+  extern __shared__ __attribute__((aligned(16))) float fs_tile[];
+  __shared__ unsigned s_mask[FS_MASK_CHUNK];
+  __shared__ int s_cnt[FS_MASK_CHUNK];
+  __shared__ float s_prior[FS_MAX_C];
+  const int tid = threadIdx.x, FC = F * C, stride = FC | 1;
+  const unsigned magic = 0xFFFFFFFFu / (unsigned)FC + 1u;
+  const unsigned fmask = F == 32 ? ~0u : (1u << F) - 1u;
+  const int ntiles = (N + TR - 1) / TR;
+  if (tid < C) s_prior[tid] = log_prior[tid];
+  for (int b0 = blockIdx.y * mchunk; b0 < B; b0 += gridDim.y * mchunk) {
+    const int nb = min(mchunk, B - b0);
+    for (int j = tid; j < nb; j += 256) {
+      s_mask[j] = masks[b0 + j] & fmask;
+      s_cnt[j] = 0;
+    }
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+      const long long n0 = (long long)t * TR;
+      const int nr = min(TR, N - (int)n0);
+      fs_stage(fs_tile, LL, n0, nr, FC, stride, magic, tid, 256);
+      __syncthreads();
+      fs_score_tile(fs_tile, stride, TR, nr, s_prior, F, C, labels + n0, s_mask, nullptr, nb, s_cnt, tid, 256);
+      __syncthreads();
+    }
+    for (int j = tid; j < nb; j += 256) {
+      const int c = s_cnt[j];
+      if (c) atomicAdd(&out[b0 + j], c);
+    }
+  }
+}
+
+// ---- island GA over feature subsets ------------------------------------------------------------
+// The frame of ga_meeting_kernel (pools, children and costs in LDS for all G generations, Philox by
+// global island index, lane c < 2r of wave 0 builds and mutates child c of pair c >> 1 from the same
+// Philox words), with a solution held as one 32-bit mask:
+//   * valid: min_size <= popcount <= max_size; mutation flips one bit (the value draw of the
+//     shared counter layout is unused), redrawn up to GA_MAX_TRY times until the child is valid;
+//   * the crossover cut lies in [1, F) (none at F = 1);
+//   * cost: every wave of the workgroup then scores the valid children over the N rows, tile by
+//     tile, into integer LDS counters; cost = (float)errors / (float)N, `invalid` for an invalid child.
+// pop stays int16 [islands][P][F] of 0 / 1 at the interface; it is packed on entry and unpacked
+// on exit.  The workgroup has blockDim.x = 256 or 1,024 threads; no result depends on it.
+// optimize/ga_subset.py::ga_subset_reference is the bit-exact host twin.
+__global__ __launch_bounds__(1024) void ga_subset_kernel(
+    const float* __restrict__ LL, const float* __restrict__ log_prior, const int* __restrict__ labels, int N, int F,
+    int C, int min_size, int max_size, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
+    float* __restrict__ hist, int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
+    long long island_base, unsigned long long gen_base, int TR) {
+  extern __shared__ __attribute__((aligned(16))) float fs_tile[];
+  __shared__ unsigned s_pool[2][64], s_kid[64];
+  __shared__ float s_pc[2][64], s_kc[64], s_prior[FS_MAX_C];
+  __shared__ int s_ord[64], s_kord[64], s_nsrc[64], s_cnt[64], s_vk[64], s_nv;
+  unsigned *pa = s_pool[0], *pb = s_pool[1];
+  float *pc = s_pc[0], *pc2 = s_pc[1];
+  const int tid = threadIdx.x, nt = blockDim.x, FC = F * C, stride = FC | 1;
+  const unsigned magic = 0xFFFFFFFFu / (unsigned)FC + 1u;
+  const int ntiles = (N + TR - 1) / TR;
+  const long long isl = blockIdx.x;
+  const unsigned long long gi = (unsigned long long)(island_base + isl);
+  short* gpop = pop + isl * P * F;
+  if (tid < P) {
+    unsigned mk = 0;
+    for (int f = 0; f < F; ++f) mk |= (unsigned)(gpop[tid * F + f] != 0) << f;
+    pa[tid] = mk;
+    pc[tid] = pop_cost[isl * P + tid];
+  }
+  if (tid < C) s_prior[tid] = log_prior[tid];
+  bool staged = false;
+  __syncthreads();
+  for (int g = 0; g < G; ++g) {
+    // 1. rank
+    ga_rank(pc, P, tid, s_ord);
+    __syncthreads();
+    if (tid == 0) hist[isl * G + g] = pc[s_ord[0]];
+    // 2. wave 0: lane c builds and mutates child c of pair c >> 1; the valid children are listed in s_vk
+    bool ok = false;
+    if (tid < 64) {
+      if (tid < 2 * r) {
+        const int h = tid & 1;
+        const unsigned long long ctr = 256ull * (gen_base + (unsigned long long)g) + (unsigned long long)(tid >> 1);
+        const av::u4 R = av::philox_draw(seed, ctr, gi);
+        const int a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
+        int b = 0;
+        if (m > 1) {
+          b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
+          b += b >= a;
+        }
+        const int cut = F > 1 ? 1 + min((int)(av::u32_to_unit(R.z) * (float)(F - 1)), F - 2) : 0;
+        const unsigned low = (1u << cut) - 1u;  // cut <= 31
+        const unsigned A = pa[s_ord[h ? b : a]], Bm = pa[s_ord[h ? a : b]];  // head, tail
+        unsigned c = (A & low) | (Bm & ~low);
+        if (mutate) {
+          for (int t = 0;; ++t) {
+            const av::u4 Q = av::philox_draw(seed ^ 0xD1B54A32D192ED03ull, ctr * 16ull + (unsigned long long)t, gi);
+            const int pos = min((int)(av::u32_to_unit(h == 0 ? Q.x : Q.z) * (float)F), F - 1);
+            c ^= 1u << pos;
+            const int sz = __popc(c);
+            ok = sz >= min_size && sz <= max_size;
+            if (ok || t == GA_MAX_TRY - 1) break;
+            c ^= 1u << pos;
+          }
+        } else {
+          const int sz = __popc(c);
+          ok = sz >= min_size && sz <= max_size;
+        }
+        s_kid[tid] = c;
+        s_kc[tid] = invalid;
+        s_cnt[tid] = 0;
+      }
+      const unsigned long long vb = __ballot(ok);
+      if (ok) s_vk[__popcll(vb & ((1ull << tid) - 1ull))] = tid;
+      if (tid == 0) s_nv = __popcll(vb);
+    }
+    __syncthreads();
+    // 3. all waves: the valid children over the N rows
+    const int nv = s_nv;
+    if (nv)
+      for (int t = 0; t < ntiles; ++t) {
+        const long long n0 = (long long)t * TR;
+        const int nr = min(TR, N - (int)n0);
+        if (ntiles > 1 || !staged) {  // a single tile stays staged for the whole launch
+          fs_stage(fs_tile, LL, n0, nr, FC, stride, magic, tid, nt);
+          staged = true;
+          __syncthreads();
+        }
+        fs_score_tile(fs_tile, stride, TR, nr, s_prior, F, C, labels + n0, s_kid, s_vk, nv, s_cnt, tid, nt);
+        __syncthreads();
+      }
+    if (ok) s_kc[tid] = (float)s_cnt[tid] / (float)N;
+    __syncthreads();
+    ga_rank(s_kc, 2 * r, tid, s_kord);
+    __syncthreads();
+    // 4. replacement
+    ga_replace(pa, pb, s_kid, pc, pc2, s_kc, s_ord, s_kord, s_nsrc, P, 1, r, purge_first, tid, nt);
+    unsigned* tp = pa; pa = pb; pb = tp;
+    float* tc = pc; pc = pc2; pc2 = tc;
+  }
+  for (int e = tid; e < P * F; e += nt) {
+    const int p = e / F;
+    gpop[e] = (short)((pa[p] >> (e - p * F)) & 1u);
+  }
+  if (tid < P) pop_cost[isl * P + tid] = pc[tid];
+}
+
 }  // namespace
 
 namespace avk {
@@ -529,6 +814,51 @@ void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* po
   if (islands <= 0 || G <= 0) return;
   ga_meeting_kernel<<<islands, 64, lds, stream>>>(dom, invalid, pop, pop_cost, hist, P, G, m, r, purge_first, mutate,
                                                   seed, island_base, gen_base);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+static void fs_check(int N, int F, int C, const char* who) {
+  if (F < 1 || F > 32 || C < 2 || C > FS_MAX_C || N < 1 || N >= (1 << 24))
+    throw std::invalid_argument(std::string(who) + ": 1 <= F <= 32, 2 <= C <= 16, 1 <= N < 2^24");
+}
+
+int ga_subset_threads(int N) { return N > 2048 ? 1024 : 256; }
+
+size_t ga_subset_lds(int N, int F, int C) {
+  const int FC = F * C;
+  return (size_t)fs_tile_rows(FC, ga_subset_threads(N)) * (FC | 1) * sizeof(float);
+}
+
+void subset_errors(const float* LL, const float* log_prior, const int* labels, int N, int F, int C,
+                   const unsigned* masks, int B, int* out, hipStream_t stream) {
+  fs_check(N, F, C, "subset_errors");
+  if (B <= 0) return;
+  AV_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * sizeof(int), stream));
+  const int FC = F * C, TR = fs_tile_rows(FC, 256);
+  const int ntiles = (N + TR - 1) / TR;
+  const size_t lds = (size_t)TR * (FC | 1) * sizeof(float);
+  // about 1,024 workgroups: row tiles first, then chunks of at least 16 masks
+  const int gx = std::min(ntiles, 1024);
+  const int mchunk = std::min(FS_MASK_CHUNK, std::max(16, (B + 1024 / gx - 1) / (1024 / gx)));
+  const int gy = std::min((B + mchunk - 1) / mchunk, 1024);
+  subset_errors_kernel<<<dim3(gx, gy), 256, lds, stream>>>(LL, log_prior, labels, N, F, C, masks, B, out, TR, mchunk);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+void ga_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, float invalid, short* pop, float* pop_cost, float* hist, int islands, int P, int G, int m,
+               int r, int purge_first, int mutate, unsigned long long seed, long long island_base,
+               unsigned long long gen_base, hipStream_t stream) {
+  fs_check(N, F, C, "ga_subset");
+  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P)
+    throw std::invalid_argument("ga_subset: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
+  if (!purge_first && P + r > 64) throw std::invalid_argument("ga_subset: P + r <= 64 when children join the pool");
+  if (islands <= 0 || G <= 0) return;
+  const int FC = F * C, nt = ga_subset_threads(N), TR = fs_tile_rows(FC, nt);
+  const size_t lds = (size_t)TR * (FC | 1) * sizeof(float);
+  ga_subset_kernel<<<islands, nt, lds, stream>>>(LL, log_prior, labels, N, F, C, min_size, max_size, invalid, pop,
+                                                 pop_cost, hist, P, G, m, r, purge_first, mutate, seed, island_base,
+                                                 gen_base, TR);
   AV_HIP_CHECK(hipGetLastError());
 }
 

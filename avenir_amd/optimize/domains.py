@@ -245,5 +245,20 @@ class FeatureSubsetDomain(SearchDomain):
         pred = scores.argmax(2)
         return (pred != self.labels.view(1, -1)).float().mean(1)
 
+    def errors(self, sol):
+        """Exact mis-prediction counts int64 [P] of the subsets ``sol`` [P, F] under the built-in
+        evaluator, scores summed feature by feature in fp32 (optimize/ga_subset.py:
+        ``subset_errors_kernel`` when the domain is on a GPU, its host twin otherwise)."""
+        from .ga_subset import subset_errors_device, subset_errors_reference, subset_tables
+        tables = subset_tables(self)
+        if tables is None:
+            raise ValueError("errors() needs the built-in evaluator within the subset kernel's limits")
+        bits = torch.arange(self.F, device=sol.device)
+        packed = ((sol != 0).long() << bits).sum(1)                                       # [P] in [0, 2^32)
+        if self.device.type != "cuda":
+            return torch.from_numpy(subset_errors_reference(tables, packed.cpu().numpy())).to(sol.device)
+        packed = torch.where(packed >= (1 << 31), packed - (1 << 32), packed).to(torch.int32)
+        return subset_errors_device(tables, packed.to(self.device)).long().to(sol.device)
+
     def decode(self, sol):
         return [row.nonzero().view(-1).tolist() for row in sol]

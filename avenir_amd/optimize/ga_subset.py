@@ -1,0 +1,294 @@
+"""Island genetic algorithm over feature subsets scored by naive Bayes as ONE kernel launch (K22,
+``csrc/kernels/optim.hip::ga_subset_kernel``), the scoring on its own
+(``subset_errors_kernel``) and their bit-exact host twins.
+
+Reference: feature selection is the second population-search application of the reference
+(P/app/fesel.py driven by P/mlextra/optpopu.py:98-187).  The frame is the one of
+:mod:`~avenir_amd.optimize.ga_meeting`: every island is one workgroup whose pool, costs and children
+stay in LDS for all G generations of a launch, and its random stream is Philox keyed by the island's
+GLOBAL index.  What differs is the domain:
+
+* a solution is a 32-bit mask over F <= 32 features (int16 0 / 1 rows at the interface), valid when
+  ``min_size <= popcount <= max_size``; mutation flips one bit;
+* the cost is the naive-Bayes error of the subset: with per-row, per-feature, per-class
+  log-likelihoods ``LL [N, F, C]`` the score of row n and class c is ``log_prior[c]`` plus
+  ``LL[n, f, c]`` over the included features, f ascending, one fp32 add each; the prediction is the
+  first class with the largest score and the cost is ``(float)errors / (float)N``.  The error count
+  is an integer, so it depends on no tile, grid or workgroup size.
+
+:func:`subset_tables` compiles a :class:`~avenir_amd.optimize.domains.FeatureSubsetDomain` with the
+built-in evaluator into the kernels' tables (or ``None``); :func:`subset_errors_reference` and
+:func:`ga_subset_reference` replay the kernels in numpy — same Philox counters, same fp32 adds in the
+same order, same (cost, index) orderings — so GPU output equals them bit for bit.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..ops.random import philox4x32, u32_to_unit
+from .ga import _INIT_KEY, _MAX_TRY, _MUT_KEY, _unit_index
+
+MAX_F, MAX_C, MAX_N = 32, 16, 1 << 24                   # the kernels' limits: F <= 32, C <= 16, N < 2^24
+# GeneticAlgorithm takes the island engine up to this many rows (search._island_engine): the largest
+# size at which one island still beat the generic path (profiles/ga_subset_cap_sweep.jsonl)
+ROW_CAP = 1 << 15
+_F = np.float32
+
+
+def ga_subset_lds(N: int, F: int, C: int) -> int:
+    """Bytes of dynamic LDS per island (``avk::ga_subset_lds``): the row tile, a power of two of at
+    most 256 (N <= 2048) or 1,024 rows of odd stride ``F C | 1`` within 48 KiB, at least 16 rows."""
+    tr = 1024 if N > 2048 else 256
+    stride = (F * C) | 1
+    while tr > 16 and tr * stride * 4 > 48 * 1024:
+        tr >>= 1
+    return tr * stride * 4
+
+
+def _key(domain) -> tuple:
+    t = (domain.loglik, domain.log_prior, domain.labels)
+    return tuple((id(x), x._version) for x in t) + (domain.min_size, domain.max_size)
+
+
+def subset_tables(domain) -> dict | None:
+    """The kernels' tables of a FeatureSubsetDomain with the built-in naive-Bayes evaluator, or
+    ``None``: a ``cost_fn``, no ``loglik``, tied ``groups``, a shape outside the limits (1 <= F <= 32,
+    2 <= C <= 16, 1 <= N < 2^24, labels in int32) or a non-finite value in ``loglik`` / ``log_prior``
+    (``-inf`` too).  The tables are kept on the domain while its tensors stay unchanged."""
+    from .domains import FeatureSubsetDomain
+    if not isinstance(domain, FeatureSubsetDomain) or domain.cost_fn is not None or domain.groups:
+        return None
+    ll, lp, lab = domain.loglik, domain.log_prior, domain.labels
+    if ll is None or lp is None or lab is None or ll.dim() != 3:
+        return None
+    key = _key(domain)
+    hit = domain.__dict__.get("_subset_tables")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    N, F, C = ll.shape
+    tables = None
+    if (1 <= F <= MAX_F and F == domain.F and 2 <= C <= MAX_C and 1 <= N < MAX_N and lp.numel() == C
+            and lab.numel() == N and 0 <= domain.min_size <= min(domain.max_size, MAX_F)
+            and bool(torch.isfinite(ll).all()) and bool(torch.isfinite(lp).all())
+            and int(lab.min()) >= -(1 << 31) and int(lab.max()) < (1 << 31)):
+        dll = ll.detach().float().contiguous()
+        dlp = lp.detach().float().reshape(-1).contiguous()
+        dlab = lab.detach().reshape(-1).to(torch.int32).contiguous()
+        tables = {
+            "N": int(N), "F": int(F), "C": int(C),
+            "LL": np.ascontiguousarray(dll.cpu().numpy()), "log_prior": np.ascontiguousarray(dlp.cpu().numpy()),
+            "labels": np.ascontiguousarray(dlab.cpu().numpy()),
+            "min_size": int(domain.min_size), "max_size": min(int(domain.max_size), MAX_F),
+            "invalid": float(domain.invalid_cost), "_device": {},
+        }
+        if ll.device.type == "cuda":                       # the domain's own tensors serve its device
+            tables["_device"][_dev_key(ll.device)] = [dll, dlp, dlab]
+    domain.__dict__["_subset_tables"] = (key, tables)
+    return tables
+
+
+def _dev_key(device: torch.device) -> str:
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        return f"cuda:{torch.cuda.current_device()}"
+    return str(device)
+
+
+def _device_tables(tables: dict, device: torch.device) -> list[torch.Tensor]:
+    cache = tables.setdefault("_device", {})
+    key = _dev_key(device)
+    if key not in cache:
+        cache[key] = [torch.from_numpy(tables[k]).to(device) for k in ("LL", "log_prior", "labels")]
+    return cache[key]
+
+
+def pack_masks(sol) -> np.ndarray:
+    """0 / 1 rows [..., F] -> uint32 masks [...] (bit f = column f)."""
+    s = np.asarray(sol)
+    w = np.uint64(1) << np.arange(s.shape[-1], dtype=np.uint64)
+    return ((s != 0).astype(np.uint64) * w).sum(-1).astype(np.uint32)
+
+
+def unpack_masks(masks, F: int) -> np.ndarray:
+    """uint32 masks [...] -> int16 0 / 1 rows [..., F]."""
+    mk = np.asarray(masks, dtype=np.uint32)
+    return ((mk[..., None] >> np.arange(F, dtype=np.uint32)) & np.uint32(1)).astype(np.int16)
+
+
+def _as_masks(masks) -> np.ndarray:
+    if isinstance(masks, torch.Tensor):
+        masks = masks.detach().cpu().numpy()
+    mk = np.asarray(masks)
+    if mk.dtype == np.int32:
+        return mk.view(np.uint32).reshape(-1)
+    if mk.size and (mk.min() < 0 or mk.max() >= (1 << 32)):
+        raise ValueError("masks must fit 32 bits")
+    return mk.astype(np.uint32).reshape(-1)
+
+
+def _field(F: int) -> np.uint32:
+    return np.uint32(0xFFFFFFFF if F == 32 else (1 << F) - 1)
+
+
+def subset_errors_reference(tables: dict, masks) -> np.ndarray:
+    """Host twin of ``subset_errors_kernel``: int64 [B] rows mis-predicted under each 32-bit mask.
+    Scores [N, C] start at the prior and, for f ascending, become
+    ``np.where(bit_f, (s + LL[:, f, :]).astype(float32), s)`` — for one mask at a time that is an
+    fp32 add for every set bit and nothing otherwise; the first maximum over the classes predicts.
+    Equal masks are scored once."""
+    mk = _as_masks(masks) & _field(tables["F"])
+    lp, lab = tables["log_prior"], tables["labels"]
+    N, F, C = tables["LL"].shape
+    if "_LLT" not in tables:                                 # [F, N, C]: one contiguous slab per feature
+        tables["_LLT"] = np.ascontiguousarray(tables["LL"].transpose(1, 0, 2))
+    llt = tables["_LLT"]
+    uniq, inv = np.unique(mk, return_inverse=True)
+    err = np.zeros(uniq.size, dtype=np.int64)
+    for i, u in enumerate(uniq.tolist()):
+        s = np.broadcast_to(lp[None, :], (N, C)).astype(np.float32)
+        for f in range(F):
+            if (u >> f) & 1:
+                np.add(s, llt[f], out=s)
+        err[i] = np.count_nonzero(s.argmax(1) != lab)
+    return err[inv.reshape(-1)]
+
+
+def subset_errors(tables: dict, masks, device="cpu") -> np.ndarray:
+    """Error counts int64 [B] of 32-bit masks: ``subset_errors_kernel`` on a GPU, the twin on the host."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return subset_errors_reference(tables, masks)
+    mk = torch.from_numpy(_as_masks(masks).view(np.int32).copy()).to(device)
+    return subset_errors_device(tables, mk).cpu().numpy().astype(np.int64)
+
+
+def subset_errors_device(tables: dict, masks: torch.Tensor) -> torch.Tensor:
+    """``subset_errors_kernel`` on int32 masks [B] resident on a GPU -> int32 [B] on that GPU."""
+    from .. import _native
+    return _native.C().subset_errors(*_device_tables(tables, masks.device), masks.contiguous())
+
+
+def ga_subset_valid(tables: dict, masks) -> np.ndarray:
+    """min_size <= popcount <= max_size of uint32 masks [...] -> bool [...]."""
+    mk = np.asarray(masks, dtype=np.uint32)
+    n = unpack_masks(mk, 32).sum(-1)
+    return (n >= tables["min_size"]) & (n <= tables["max_size"])
+
+
+def ga_subset_price(tables: dict, masks, device="cpu") -> np.ndarray:
+    """Cost float32 [...] of uint32 masks [...]: ``(float)errors / (float)N``, the domain's invalid
+    cost for an invalid mask (which is not scored)."""
+    mk = np.asarray(masks, dtype=np.uint32)
+    ok = ga_subset_valid(tables, mk)
+    cost = np.full(mk.shape, _F(tables["invalid"]), dtype=np.float32)
+    if ok.any():
+        err = subset_errors(tables, mk[ok], device)
+        cost[ok] = err.astype(np.float32) / _F(tables["N"])
+    return cost
+
+
+def ga_subset_init(tables: dict, n_islands: int, P: int, seed: int, island_base: int, max_try: int = 40) -> np.ndarray:
+    """Initial pools [islands, P, F] int16 of 0 / 1, host-side per global island: member p of island
+    gi, attempt a, position l is min((int)(2 u), 1) with u from Philox(seed ^ INIT, (p F + l) 64 + a, gi).x;
+    the whole member is redrawn while it is invalid (up to ``max_try`` <= 64 attempts, the last one stays)."""
+    if not 1 <= max_try <= 64:
+        raise ValueError("max_try must lie in [1, 64]")
+    L = tables["F"]
+    out = np.zeros((n_islands, P, L), dtype=np.int64)
+    ti, tp = (x.reshape(-1) for x in np.meshgrid(np.arange(n_islands), np.arange(P), indexing="ij"))
+    pos = np.arange(L, dtype=np.uint64)[None, :]
+    for a in range(max_try):
+        if ti.size == 0:
+            break
+        off = (tp.astype(np.uint64)[:, None] * np.uint64(L) + pos) * np.uint64(64) + np.uint64(a)
+        gis = np.broadcast_to((ti + island_base).astype(np.uint64)[:, None], off.shape)
+        x, _, _, _ = philox4x32(seed ^ _INIT_KEY, off, gis)
+        draw = _unit_index(u32_to_unit(x), 2)
+        out[ti, tp] = draw
+        bad = ~ga_subset_valid(tables, pack_masks(draw))
+        ti, tp = ti[bad], tp[bad]
+    return out.astype(np.int16)
+
+
+def ga_subset_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
+                        purge_first: bool, mutate: bool, seed: int, island_base: int,
+                        gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host twin of ``ga_subset_kernel`` (all islands at once).  Returns (pop int16, cost float32,
+    hist float32)."""
+    F = tables["F"]
+    mk = pack_masks(pop)                                             # [I, P] uint32
+    pc = np.array(pop_cost, dtype=np.float32)
+    I, P = mk.shape
+    gis = np.arange(island_base, island_base + I, dtype=np.uint64)
+    ar = np.arange(I)
+    ii = ar[:, None]
+    gir = np.broadcast_to(gis[:, None], (I, r))
+    hist = np.zeros((I, G), dtype=np.float32)
+    for g in range(G):
+        ord_ = np.argsort(pc, axis=1, kind="stable")
+        hist[:, g] = pc[ar, ord_[:, 0]]
+        ctr = np.array([256 * (gen_base + g) + k for k in range(r)], dtype=np.uint64)[None, :]
+        x_, y_, z_, _ = philox4x32(seed, np.broadcast_to(ctr, (I, r)), gir)
+        a = _unit_index(u32_to_unit(x_), m)
+        b = np.zeros((I, r), dtype=np.int64)
+        if m > 1:
+            b = np.minimum((u32_to_unit(y_) * _F(m - 1)).astype(np.int64), m - 2)
+            b = b + (b >= a)
+        cut = np.zeros((I, r), dtype=np.int64)
+        if F > 1:
+            cut = 1 + np.minimum((u32_to_unit(z_) * _F(F - 1)).astype(np.int64), F - 2)
+        low = ((np.uint64(1) << cut.astype(np.uint64)) - np.uint64(1)).astype(np.uint32)      # cut <= 31
+        A = mk[ii, ord_[ii, a]]                                      # [I, r]
+        B = mk[ii, ord_[ii, b]]
+        pair = [(A & low) | (B & ~low), (B & low) | (A & ~low)]
+        if mutate:
+            for h, c in enumerate(pair):
+                done = np.zeros((I, r), dtype=bool)
+                for t in range(_MAX_TRY):
+                    if done.all():
+                        break
+                    q = philox4x32(seed ^ _MUT_KEY, np.broadcast_to(ctr * np.uint64(16) + np.uint64(t), (I, r)), gir)
+                    pos = _unit_index(u32_to_unit(q[0] if h == 0 else q[2]), F)     # the value draw is unused:
+                    cand = c ^ (np.uint32(1) << pos.astype(np.uint32))              # a 0 / 1 position flips
+                    take = ~done & ((t == _MAX_TRY - 1) | ga_subset_valid(tables, cand))
+                    c[take] = cand[take]
+                    done |= take
+        kids = np.stack(pair, axis=2).reshape(I, 2 * r)              # child 2k, 2k + 1 of pair k
+        kc = ga_subset_price(tables, kids)
+        kord = np.argsort(kc, axis=1, kind="stable")
+        if purge_first:
+            nsrc = np.concatenate([ord_[:, : P - r], P + kord[:, :r]], axis=1)
+        else:
+            src = np.concatenate([np.broadcast_to(np.arange(P), (I, P)), P + kord[:, :r]], axis=1)
+            cc = np.concatenate([pc, kc[ii, kord[:, :r]]], axis=1)
+            nsrc = np.take_along_axis(src, np.argsort(cc, axis=1, kind="stable")[:, :P], axis=1)
+        mk = np.concatenate([mk, kids], axis=1)[ii, nsrc]
+        pc = np.concatenate([pc, kc], axis=1)[ii, nsrc]
+    return unpack_masks(mk, F), pc, hist
+
+
+def ga_subset_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool,
+                  mutate: bool, seed: int, island_base: int, device: torch.device, gen_base: int = 0):
+    """Advance the islands G generations (counters from ``gen_base``) on ``device``: the kernel on the
+    GPU, the twin on the host.  ``domain`` is a FeatureSubsetDomain or its :func:`subset_tables`.
+    Returns numpy (pop int16, pop_cost float32, hist float32)."""
+    tables = domain if isinstance(domain, dict) else subset_tables(domain)
+    if tables is None:
+        raise ValueError("the domain is outside the subset kernel's limits")
+    pop = np.ascontiguousarray(pop, dtype=np.int16)
+    if pop.ndim != 3 or pop.shape[2] != tables["F"]:
+        raise ValueError("pop must be [islands, P, F]")
+    if pop.size and (pop.min() < 0 or pop.max() > 1):
+        raise ValueError("pool values must be 0 or 1")
+    device = torch.device(device)
+    if device.type == "cuda":
+        from .. import _native
+        tp = torch.from_numpy(pop).to(device)
+        tc = torch.from_numpy(np.ascontiguousarray(pop_cost, dtype=np.float32)).to(device)
+        hist = torch.empty((pop.shape[0], G), dtype=torch.float32, device=device)
+        _native.C().ga_subset(*_device_tables(tables, device), tables["min_size"], tables["max_size"],
+                              float(tables["invalid"]), tp, tc, hist, G, m, r, bool(purge_first), bool(mutate),
+                              int(seed), int(island_base), int(gen_base))
+        return tp.cpu().numpy(), tc.cpu().numpy(), hist.cpu().numpy()
+    return ga_subset_reference(tables, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)

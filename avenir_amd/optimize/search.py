@@ -434,6 +434,27 @@ class _MeetingIslands:
                               gen_base=gen_base)
 
 
+class _SubsetIslands:
+    """Island engine of a FeatureSubsetDomain with the built-in naive-Bayes evaluator:
+    ``ga_subset_kernel`` / its twin (optimize/ga_subset.py)."""
+
+    def __init__(self, tables: dict, device):
+        self.tables, self.device = tables, device
+
+    def name(self, device) -> str:
+        return "ga_subset_kernel" if device.type == "cuda" else "ga_subset_host"
+
+    def init(self, n: int, P: int, seed: int, island_base: int):
+        from .ga_subset import ga_subset_init, ga_subset_price, pack_masks
+        pop = ga_subset_init(self.tables, n, P, seed, island_base)
+        return pop, ga_subset_price(self.tables, pack_masks(pop), self.device)
+
+    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
+        from .ga_subset import ga_subset_run
+        return ga_subset_run(self.tables, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
+                             gen_base=gen_base)
+
+
 class GeneticAlgorithm:
     """Island-model GA: ``islands`` independent pools advance together as one [I, pool, L] batch.
 
@@ -519,7 +540,13 @@ class GeneticAlgorithm:
         no tied groups or checkpointing, pools of <= 64, LDS <= 64 KiB per island.  Assignment
         domains take ``ga_assign_kernel`` (optimize/ga.py), on the CPU its host twin.  Meeting-schedule
         domains within the kernel's limits take ``ga_meeting_kernel`` (optimize/ga_meeting.py) on a
-        GPU; on the CPU its twin runs only when ``use_kernel`` is True, so CPU results are unchanged."""
+        GPU; on the CPU its twin runs only when ``use_kernel`` is True, so CPU results are unchanged.
+        Under the same rule, feature-subset domains with the built-in naive-Bayes evaluator take
+        ``ga_subset_kernel`` (optimize/ga_subset.py) up to ``ga_subset.ROW_CAP`` = 2^15 data rows:
+        one workgroup streams every row once per generation, so a single island is bound by one
+        CU.  Measured at 1 island (churn model, 100 generations, profiles/ga_subset_cap_sweep.jsonl)
+        the kernel run takes 46 ms against 66 ms at 2^15 rows and 92 ms against 69 ms at 2^16, so
+        above the cap the generic path stays (with 64 islands the kernel still wins at 2^20 rows)."""
         d = self.d
         if self.use_kernel is False or getattr(d, "groups", None) or self.recovery is not None:
             return None
@@ -534,6 +561,11 @@ class GeneticAlgorithm:
             tables = meeting_tables(d)      # None unless a MeetingScheduleDomain within the kernel's limits
             if tables is not None and ga_meeting_lds(P, d.L, r) <= 64 * 1024:
                 return _MeetingIslands(tables)
+            from .ga_subset import ROW_CAP, ga_subset_lds, subset_tables
+            if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3 and d.loglik.shape[0] <= ROW_CAP:
+                tables = subset_tables(d)   # None unless a FeatureSubsetDomain with the built-in evaluator
+                if tables is not None and ga_subset_lds(tables["N"], tables["F"], tables["C"]) <= 48 * 1024:
+                    return _SubsetIslands(tables, d.device)
         return None
 
     def _run_islands(self, comm, engine) -> OptResult:
