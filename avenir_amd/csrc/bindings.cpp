@@ -1422,27 +1422,41 @@ void sa_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict
                  cur_stream(cost));
 }
 
-void ga_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, double invalid, at::Tensor& pop,
-               at::Tensor& pop_cost, at::Tensor& hist, int64_t G, int64_t m, int64_t r, bool purge_first, bool mutate,
-               bool swap, int64_t seed, int64_t island_base, int64_t gen_base) {
+// The checks shared by the island GA bindings (optim.hip): pop int16 [islands, P, L] with its costs
+// and hist [islands, G] on one device, the kernels' pool limits and the generation counters.
+// Returns (islands, P).
+static std::pair<int64_t, int64_t> ga_check(const char* who, const at::Tensor& pop, int64_t L,
+                                            const at::Tensor& pop_cost, const at::Tensor& hist, int64_t G, int64_t m,
+                                            int64_t r, bool purge_first, int64_t gen_base) {
+  TORCH_CHECK(G >= 0 && gen_base >= 0 && gen_base + G < (1LL << 40), who, ": generation counter out of range");
+  CHECK_DEV(pop);
+  CHECK_DTYPE(pop, at::kShort);
+  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == L && pop.is_contiguous(), who, ": pop must be contiguous [islands, P, ",
+              L, "]");
+  const int64_t I = pop.size(0), P = pop.size(1);
+  TORCH_CHECK(I < (1LL << 31), who, ": too many islands");
+  avk::ga_check_pool(who, P, m, r, purge_first);
+  CHECK_DEV(pop_cost);
+  CHECK_DTYPE(pop_cost, at::kFloat);
+  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, who, ": pop_cost must be [islands, P]");
+  CHECK_DEV(hist);
+  CHECK_DTYPE(hist, at::kFloat);
+  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, who, ": hist must be [islands, G]");
+  TORCH_CHECK(pop_cost.device() == pop.device() && hist.device() == pop.device(), who, ": tensors on one device");
+  return {I, P};
+}
+
+void ga_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, double invalid, bool swap,
+               at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& hist, int64_t G, int64_t m, int64_t r,
+               bool purge_first, bool mutate, int64_t seed, int64_t island_base, int64_t gen_base) {
   CHECK_DEV(cost);
   CHECK_DTYPE(cost, at::kFloat);
   TORCH_CHECK(cost.dim() == 2 && cost.size(1) >= 2 && cost.is_contiguous(), "cost must be contiguous [L, V>=2]");
-  TORCH_CHECK(gen_base >= 0 && gen_base + G < (1LL << 40), "generation counter out of range");
   const int64_t L = cost.size(0), V = cost.size(1);
   TORCH_CHECK(V <= 32767, "V too large");
-  CHECK_DEV(pop);
-  CHECK_DTYPE(pop, at::kShort);
-  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == L && pop.is_contiguous(), "pop must be contiguous [islands, P, L]");
-  const int64_t I = pop.size(0), P = pop.size(1);
+  const auto [I, P] = ga_check("ga_assign", pop, L, pop_cost, hist, G, m, r, purge_first, gen_base);
   if (pop.numel())
     TORCH_CHECK(pop.min().item<int>() >= 0 && pop.max().item<int>() < V, "solution values out of range");
-  CHECK_DEV(pop_cost);
-  CHECK_DTYPE(pop_cost, at::kFloat);
-  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, "pop_cost must be [islands, P]");
-  CHECK_DEV(hist);
-  CHECK_DTYPE(hist, at::kFloat);
-  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, "hist must be [islands, G]");
   const uint8_t* cf = nullptr;
   if (conflict.has_value() && conflict->defined()) {
     CHECK_DEV((*conflict));
@@ -1455,8 +1469,7 @@ void ga_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict
   avk::ga_assign(cost.data_ptr<float>(), (int)L, (int)V, cf, (float)invalid, pop.data_ptr<int16_t>(),
                  pop_cost.data_ptr<float>(), hist.data_ptr<float>(), (int)I, (int)P, (int)G, (int)m, (int)r,
                  purge_first ? 1 : 0, mutate ? 1 : 0, swap ? 1 : 0, (unsigned long long)seed, (long long)island_base,
-                 (int)gen_base,
-                 cur_stream(cost));
+                 (unsigned long long)gen_base, cur_stream(cost));
 }
 
 // island GA over a meeting-schedule domain (optim.hip::ga_meeting_kernel).  The domain tensors are
@@ -1486,22 +1499,9 @@ void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tenso
   TORCH_CHECK(share.numel() == M, "share must be [M]");
   TORCH_CHECK(nd >= 1 && nd <= 32 && nh >= 1 && nh <= 32 && nm >= 1 && nm <= 32, "value tables of 1..32 entries");
   TORCH_CHECK(nb <= 16 && no <= 16, "at most 16 blocked entries and 16 ordered pairs");
-  TORCH_CHECK(gen_base >= 0 && gen_base + G < (1LL << 40), "generation counter out of range");
   const int64_t L = 3 * M;
-  CHECK_DEV(pop);
-  CHECK_DTYPE(pop, at::kShort);
-  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == L && pop.is_contiguous(), "pop must be contiguous [islands, P, 3 M]");
-  const int64_t I = pop.size(0), P = pop.size(1);
-  TORCH_CHECK(P >= 2 && P <= 64 && r >= 1 && r <= std::min<int64_t>(P, 32) && m >= 1 && m <= P,
-              "ga_meeting: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
-  TORCH_CHECK(purge_first || P + r <= 64, "ga_meeting: P + r <= 64 when children join the pool");
+  const auto [I, P] = ga_check("ga_meeting", pop, L, pop_cost, hist, G, m, r, purge_first, gen_base);
   TORCH_CHECK(avk::ga_meeting_lds((int)P, (int)L, (int)r) <= 64 * 1024, "ga_meeting: more than 64 KiB of LDS");
-  CHECK_DEV(pop_cost);
-  CHECK_DTYPE(pop_cost, at::kFloat);
-  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, "pop_cost must be [islands, P]");
-  CHECK_DEV(hist);
-  CHECK_DTYPE(hist, at::kFloat);
-  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, "hist must be [islands, G]");
   // the domain on the host: mask bits < M, pairs < M, times that stay exact in int32 and fp32
   const uint32_t mmask = M == 32 ? 0xffffffffu : ((1u << M) - 1u);
   auto host = [](const at::Tensor& t) { return t.cpu(); };
@@ -1610,24 +1610,9 @@ void ga_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tens
   subset_check(LL, log_prior, labels, "ga_subset");
   const int64_t N = LL.size(0), F = LL.size(1), C = LL.size(2);
   TORCH_CHECK(min_size >= 0 && min_size <= max_size && max_size <= 32, "ga_subset: 0 <= min_size <= max_size <= 32");
-  TORCH_CHECK(G >= 0 && gen_base >= 0 && gen_base + G < (1LL << 40), "generation counter out of range");
-  CHECK_DEV(pop);
-  CHECK_DTYPE(pop, at::kShort);
-  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == F && pop.is_contiguous(), "pop must be contiguous [islands, P, F]");
-  const int64_t I = pop.size(0), P = pop.size(1);
-  TORCH_CHECK(I < (1LL << 31), "ga_subset: too many islands");
-  TORCH_CHECK(P >= 2 && P <= 64 && r >= 1 && r <= std::min<int64_t>(P, 32) && m >= 1 && m <= P,
-              "ga_subset: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
-  TORCH_CHECK(purge_first || P + r <= 64, "ga_subset: P + r <= 64 when children join the pool");
+  const auto [I, P] = ga_check("ga_subset", pop, F, pop_cost, hist, G, m, r, purge_first, gen_base);
   TORCH_CHECK(avk::ga_subset_lds((int)N, (int)F, (int)C) <= 48 * 1024, "ga_subset: more than 48 KiB of tile LDS");
-  CHECK_DEV(pop_cost);
-  CHECK_DTYPE(pop_cost, at::kFloat);
-  TORCH_CHECK(pop_cost.is_contiguous() && pop_cost.numel() == I * P, "pop_cost must be [islands, P]");
-  CHECK_DEV(hist);
-  CHECK_DTYPE(hist, at::kFloat);
-  TORCH_CHECK(hist.is_contiguous() && hist.numel() == I * G, "hist must be [islands, G]");
-  TORCH_CHECK(pop.device() == LL.device() && pop_cost.device() == LL.device() && hist.device() == LL.device(),
-              "ga_subset: tensors on one device");
+  TORCH_CHECK(pop.device() == LL.device(), "ga_subset: tensors on one device");
   DevGuard g(LL.device());
   avk::ga_subset(LL.data_ptr<float>(), log_prior.data_ptr<float>(), labels.data_ptr<int>(), (int)N, (int)F, (int)C,
                  (int)min_size, (int)max_size, (float)invalid, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(),

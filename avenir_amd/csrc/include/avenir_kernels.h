@@ -111,12 +111,15 @@ void sample(int dist, long long n, const float* params, const float* table, int 
             unsigned long long offset, float* out, hipStream_t stream);
 
 // ---- optim.hip (K22) -----------------------------------------------------------------------
-// island GA over an assignment domain: pop [islands][P][L] and pop_cost [islands][P] in / out,
-// hist [islands][G] the best cost at each generation's start (optim.hip)
+// island GAs: pop [islands][P][L] and pop_cost [islands][P] in / out, hist [islands][G] the best
+// cost at each generation's start.  ga_check_pool throws std::invalid_argument unless
+// 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P and, when the children join the pool, P + r <= 64.
+void ga_check_pool(const char* who, long long P, long long m, long long r, bool purge_first);
+// island GA over an assignment domain (L values in [0, V) per solution)
 size_t ga_assign_lds(int P, int L, int r);
 void ga_assign(const float* cost, int L, int V, const uint8_t* conflict, float invalid, short* pop, float* pop_cost,
                float* hist, int islands, int P, int G, int m, int r, int purge_first, int mutate, int swap,
-               unsigned long long seed, long long island_base, int gen_base, hipStream_t stream);
+               unsigned long long seed, long long island_base, unsigned long long gen_base, hipStream_t stream);
 // island GA over a meeting-schedule domain: a solution is (day, hour, minute) index triples of M
 // meetings (L = 3 M) into the integer value tables; share / member / blocked masks have one bit per
 // meeting, blocked is [nb][3] (mask, begin s, end s), ordered [no][2] (a before b)

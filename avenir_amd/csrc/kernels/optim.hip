@@ -110,40 +110,66 @@ __global__ __launch_bounds__(64) void sa_assign_kernel(
   }
 }
 
-// ---- island genetic algorithm: one workgroup (one wave) per island, G generations per launch ----
+// ---- island genetic algorithm: one workgroup per island, G generations per launch ---------------
 // Reference: Spark GA — an independent GA per partition (S/optimize/GeneticAlgorithm.scala:70-163) —
 // and the Python GeneticAlgorithmOptimizer (P/mlextra/optpopu.py:98-187: pool, mating list,
-// replacement, purge).  An island's pool [P][L], its costs and the children of a generation live in
-// LDS; per generation, one lane per member / pair / child:
+// replacement, purge).  An island's pool of P solutions, its costs and the 2r children of a
+// generation live in LDS for all G generations; per generation, one lane per member / child:
 //   1. rank the pool by (cost, index) (lane j counts the members ahead of member j) -> ord[];
 //      hist[g] = the best cost at the generation's start;
-//   2. pair k < r draws Philox(seed, 256 (gen_base + g) + k, island): parents ord[a], ord[b] (a != b) from the
-//      m best, crossover point x in [1, L), children a[:x] b[x:] and b[:x] a[x:]; with `mutate`,
-//      Philox(seed ^ M, 16 ctr + try, island) moves one position of each child to a different
-//      value (a swap move with `swap`), retried until the child is valid (<= 10 tries);
-//   3. lane c < 2r prices child c: fp32 sum of C[l][s_l] in position order times 1/L, or
-//      `invalid` when two conflicting positions share a value;
+//   2. lane c < 2r breeds child c of pair k = c >> 1.  Both lanes of a pair draw
+//      Philox(seed, 256 (gen_base + g) + k, island): parents ord[a], ord[b] (a != b) from the m best
+//      and a crossover cut; child 2k is a's head with b's tail, child 2k + 1 b's head with a's tail.
+//      With `mutate`, attempt t of the pair draws Philox(seed ^ MUT, 16 ctr + t, island): words
+//      (x, y) give position and value for child 2k, (z, w) for child 2k + 1, so the two children
+//      are mutated independently; an attempt that leaves the child invalid is taken back and
+//      redrawn, the last of GA_MAX_TRY attempts stays (BasicSearchDomain.mutateSolution);
+//   3. the child is priced (`invalid` for an invalid one) -> kc[c], and the children are ranked;
 //   4. the best r children by (cost, index) replace the worst r members (purge_first) or join the
 //      pool, whose best P by (cost, index; members before children) survive — written to the other
 //      pool buffer in rank order.
 // The island's stream is keyed by its GLOBAL index (island_base + blockIdx.x), so any world size
-// yields the same islands; optimize/ga.py::ga_assign_reference is the bit-exact host twin.
+// yields the same islands.  What a solution is, when it is valid and what it costs is the domain's:
+// each kernel below supplies steps 2 and 3 as its `breed` callable.  optimize/ga.py::
+// ga_islands_reference is the frame's bit-exact host twin.
 constexpr int GA_MAX_TRY = 10;
+constexpr unsigned long long GA_MUT_KEY = 0xD1B54A32D192ED03ull;
 
-__device__ __forceinline__ bool ga_valid(const short* s, int L, const uint8_t* __restrict__ conflict) {
-  if (conflict)
-    for (int i = 0; i < L; ++i)
-      for (int j = i + 1; j < L; ++j)
-        if (s[i] == s[j] && conflict[(long long)i * L + j]) return false;
-  return true;
-}
+struct GaArgs {
+  int P, G, m, r, purge_first, mutate;
+  unsigned long long seed;
+  long long island_base;
+  unsigned long long gen_base;
+};
 
-__device__ __forceinline__ float ga_price(const short* s, int L, int V, const float* __restrict__ cost,
-                                          const uint8_t* __restrict__ conflict, float invL, float invalid) {
-  float acc = 0.f;
-  for (int l = 0; l < L; ++l) acc += cost[(long long)l * V + s[l]];
-  return ga_valid(s, L, conflict) ? acc * invL : invalid;
-}
+__host__ __device__ constexpr size_t ga_a16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// An island's working set in LDS.  A solution is L elements of T (L shorts, or one 32-bit mask).
+template <class T>
+struct GaPool {
+  T *pa, *pb, *kid;      // [P][L] current pool, [P][L] next pool, [2r][L] children
+  float *pc, *pc2, *kc;  // [P] pool costs, [P] next pool costs, [2r] child costs
+  int *ord, *kord;       // [P] pool order, [2r] child order
+  int* nsrc;             // [P] source of next pool slot (>= P: child)
+
+  // every array 16-aligned from a 16-aligned base; returns the first byte past the view
+  __device__ __forceinline__ unsigned char* carve(unsigned char* cur, int P, int L, int r) {
+    pa = reinterpret_cast<T*>(cur);       cur += ga_a16((size_t)P * L * sizeof(T));
+    pb = reinterpret_cast<T*>(cur);       cur += ga_a16((size_t)P * L * sizeof(T));
+    kid = reinterpret_cast<T*>(cur);      cur += ga_a16((size_t)2 * r * L * sizeof(T));
+    pc = reinterpret_cast<float*>(cur);   cur += ga_a16((size_t)P * sizeof(float));
+    pc2 = reinterpret_cast<float*>(cur);  cur += ga_a16((size_t)P * sizeof(float));
+    kc = reinterpret_cast<float*>(cur);   cur += ga_a16((size_t)2 * r * sizeof(float));
+    ord = reinterpret_cast<int*>(cur);    cur += ga_a16((size_t)P * sizeof(int));
+    kord = reinterpret_cast<int*>(cur);   cur += ga_a16((size_t)2 * r * sizeof(int));
+    nsrc = reinterpret_cast<int*>(cur);   cur += ga_a16((size_t)P * sizeof(int));
+    return cur;
+  }
+  __host__ __device__ static constexpr size_t bytes(int P, int L, int r) {
+    return 2 * ga_a16((size_t)P * L * sizeof(T)) + ga_a16((size_t)2 * r * L * sizeof(T)) +
+           4 * ga_a16((size_t)P * 4) + 2 * ga_a16((size_t)2 * r * 4);  // pc, pc2, ord, nsrc; kc, kord
+  }
+};
 
 // lane j < n counts the elements ahead of element j by (cost, index) and writes ord[rank] = j
 __device__ __forceinline__ void ga_rank(const float* c, int n, int lane, int* ord) {
@@ -155,13 +181,12 @@ __device__ __forceinline__ void ga_rank(const float* c, int n, int lane, int* or
   }
 }
 
-// Step 4 of a generation (every island kernel; every thread of the workgroup calls it, `nt` of them):
-// the source of every next-pool slot -> nsrc, then the next pool pb / pc2 gathered from pa / kid.
-// A solution is L elements of T (L shorts, or one 32-bit mask).
+// Step 4 of a generation (every thread of the workgroup calls it, `nt` of them): the source of
+// every next-pool slot -> nsrc, then the next pool pb / pc2 gathered from pa / kid.
 template <class T>
 __device__ __forceinline__ void ga_replace(const T* pa, T* pb, const T* kid, const float* pc, float* pc2,
                                            const float* kc, const int* ord, const int* kord, int* nsrc, int P, int L,
-                                           int r, int purge_first, int lane, int nt = 64) {
+                                           int r, int purge_first, int lane, int nt) {
   if (purge_first) {
     if (lane < P) nsrc[lane] = lane < P - r ? ord[lane] : P + kord[lane - (P - r)];
   } else if (lane < P + r) {
@@ -190,97 +215,167 @@ __device__ __forceinline__ void ga_replace(const T* pa, T* pb, const T* kid, con
   __syncthreads();
 }
 
-__global__ __launch_bounds__(64) void ga_assign_kernel(
-    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, float invalid,
-    short* __restrict__ pop, float* __restrict__ pop_cost, float* __restrict__ hist, int P, int G, int m, int r,
-    int purge_first, int mutate, int swap, unsigned long long seed, long long island_base, int gen_base) {
-  extern __shared__ unsigned char ga_lds[];
-  short* pa = reinterpret_cast<short*>(ga_lds);   // [P][L] current pool
-  short* pb = pa + (size_t)P * L;                 // [P][L] next pool
-  short* kid = pb + (size_t)P * L;                // [2r][L] children
-  float* pc = reinterpret_cast<float*>(kid + (size_t)2 * r * L);  // [P] pool costs
-  float* pc2 = pc + P;                            // [P] next pool costs
-  float* kc = pc2 + P;                            // [2r] child costs
-  int* ord = reinterpret_cast<int*>(kc + 2 * r);  // [P] pool order
-  int* kord = ord + P;                            // [2r] child order
-  int* nsrc = kord + 2 * r;                       // [P] source of next pool slot (>= P: child)
-  const int lane = threadIdx.x;
+// Step 2's parent draw of the pair with counter ctr: a, b (ranks among the m best, a != b unless
+// m = 1) and the unit cut x in [1, ncut) (0 at ncut = 1), which the domain scales to its positions.
+struct GaPair {
+  int a, b, x;
+};
+
+__device__ __forceinline__ GaPair ga_draw_pair(unsigned long long seed, unsigned long long ctr, unsigned long long gi,
+                                               int m, int ncut) {
+  const av::u4 R = av::philox_draw(seed, ctr, gi);
+  GaPair p;
+  p.a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
+  p.b = 0;
+  if (m > 1) {
+    p.b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
+    p.b += p.b >= p.a;
+  }
+  p.x = ncut > 1 ? 1 + min((int)(av::u32_to_unit(R.z) * (float)(ncut - 1)), ncut - 2) : 0;
+  return p;
+}
+
+// Step 2's mutation of child h (0 / 1) of the pair with counter ctr.  The domain supplies
+// apply(position word, value word): one attempt; valid(): is the child valid now; undo(): take the
+// attempt back.  Returns the child's validity (without `mutate`: of the child as crossed).
+template <class Apply, class Valid, class Undo>
+__device__ __forceinline__ bool ga_mutate(const GaArgs& A, unsigned long long ctr, unsigned long long gi, int h,
+                                          Apply apply, Valid valid, Undo undo) {
+  if (!A.mutate) return valid();
+  for (int t = 0;; ++t) {
+    const av::u4 Q = av::philox_draw(A.seed ^ GA_MUT_KEY, ctr * 16ull + (unsigned long long)t, gi);
+    apply(h ? Q.z : Q.x, h ? Q.w : Q.y);
+    const bool ok = valid();
+    if (ok || t == GA_MAX_TRY - 1) return ok;
+    undo();
+  }
+}
+
+// pop [islands][P][L] int16 <-> the island's pool: L shorts per member, or the 0 / 1 row as one mask
+__device__ __forceinline__ void ga_load(short* pa, const short* gpop, int P, int L, int tid, int nt) {
+  for (int e = tid; e < P * L; e += nt) pa[e] = gpop[e];
+}
+__device__ __forceinline__ void ga_load(unsigned* pa, const short* gpop, int P, int L, int tid, int nt) {
+  if (tid < P) {
+    unsigned mk = 0;
+    for (int f = 0; f < L; ++f) mk |= (unsigned)(gpop[tid * L + f] != 0) << f;
+    pa[tid] = mk;
+  }
+}
+__device__ __forceinline__ void ga_store(short* gpop, const short* pa, int P, int L, int tid, int nt) {
+  for (int e = tid; e < P * L; e += nt) gpop[e] = pa[e];
+}
+__device__ __forceinline__ void ga_store(short* gpop, const unsigned* pa, int P, int L, int tid, int nt) {
+  for (int e = tid; e < P * L; e += nt) {
+    const int p = e / L;
+    gpop[e] = (short)((pa[p] >> (e - p * L)) & 1u);
+  }
+}
+
+// The island of this workgroup (every thread calls it, `nt` of them; P, 2r and P + r <= 64 <= nt):
+// pool in, G generations, pool out.  breed(ctr0) is steps 2 and 3 of a generation whose pair k has
+// the counter ctr0 + k: called by every thread, it leaves the children in V.kid and their costs in
+// V.kc and may hold barriers of its own; the frame's barrier follows it.  The barrier after the
+// load also covers whatever the kernel staged in LDS before the call.
+template <class T, class Breed>
+__device__ __forceinline__ void ga_island(GaPool<T>& V, const GaArgs& A, int L, short* __restrict__ pop,
+                                          float* __restrict__ pop_cost, float* __restrict__ hist, int tid, int nt,
+                                          Breed breed) {
   const long long isl = blockIdx.x;
-  const unsigned long long gi = (unsigned long long)(island_base + isl);
-  const float invL = 1.f / (float)L;
+  const int P = A.P, E = sizeof(T) == sizeof(short) ? L : 1;  // elements of T per solution
   short* gpop = pop + isl * P * L;
-  for (int e = lane; e < P * L; e += 64) pa[e] = gpop[e];
-  if (lane < P) pc[lane] = pop_cost[isl * P + lane];
+  float* ghist = hist + isl * A.G;
+  ga_load(V.pa, gpop, P, L, tid, nt);
+  if (tid < P) V.pc[tid] = pop_cost[isl * P + tid];
   __syncthreads();
-  for (int g = 0; g < G; ++g) {
+  for (int g = 0; g < A.G; ++g) {
     // 1. rank
-    ga_rank(pc, P, lane, ord);
+    ga_rank(V.pc, P, tid, V.ord);
     __syncthreads();
-    if (lane == 0) hist[isl * G + g] = pc[ord[0]];
-    // 2. children
-    if (lane < r) {
-      const unsigned long long ctr = 256ull * (unsigned long long)(gen_base + g) + lane;
-      const av::u4 R = av::philox_draw(seed, ctr, gi);
-      const int a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
-      int b = 0;
-      if (m > 1) {
-        b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
-        b += b >= a;
-      }
-      const int x = L > 1 ? 1 + min((int)(av::u32_to_unit(R.z) * (float)(L - 1)), L - 2) : 0;
-      const short* A = pa + (size_t)ord[a] * L;
-      const short* B = pa + (size_t)ord[b] * L;
-      short* c1 = kid + (size_t)(2 * lane) * L;
-      short* c2 = c1 + L;
-      for (int l = 0; l < L; ++l) {
-        c1[l] = l < x ? A[l] : B[l];
-        c2[l] = l < x ? B[l] : A[l];
-      }
-      if (mutate) {
-        // one position to a different value (with `swap`, the first other position holding that
-        // value takes the old one: the domain's swap move), redrawn up to GA_MAX_TRY times until
-        // the child is valid; the last attempt stays otherwise (BasicSearchDomain.mutateSolution)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          short* c = h == 0 ? c1 : c2;
-          for (int t = 0; t < GA_MAX_TRY; ++t) {
-            const av::u4 Q = av::philox_draw(seed ^ 0xD1B54A32D192ED03ull, ctr * 16ull + t, gi);
-            const unsigned qp = h == 0 ? Q.x : Q.z, qv = h == 0 ? Q.y : Q.w;
-            const int pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
-            const int old = c[pos];
-            int v = min((int)(av::u32_to_unit(qv) * (float)(V - 1)), V - 2);
+    if (tid == 0) ghist[g] = V.pc[V.ord[0]];
+    // 2 + 3. children and their costs
+    breed(256ull * (A.gen_base + (unsigned long long)g));
+    __syncthreads();
+    ga_rank(V.kc, 2 * A.r, tid, V.kord);
+    __syncthreads();
+    // 4. replacement
+    ga_replace(V.pa, V.pb, V.kid, V.pc, V.pc2, V.kc, V.ord, V.kord, V.nsrc, P, E, A.r, A.purge_first, tid, nt);
+    T* t = V.pa; V.pa = V.pb; V.pb = t;
+    float* tc = V.pc; V.pc = V.pc2; V.pc2 = tc;
+  }
+  ga_store(gpop, V.pa, P, L, tid, nt);
+  if (tid < P) pop_cost[isl * P + tid] = V.pc[tid];
+}
+
+// ---- island GA over an assignment domain (one wave per island) ---------------------------------
+// The frame above with:
+//   * a solution is L values in [0, V); the crossover cut x lies in [1, L);
+//   * mutation moves one position to a different value (with `swap`, the first other position
+//     holding that value takes the old one: the domain's swap move);
+//   * invalid: two conflicting positions share a value;
+//   * cost: fp32 sum of C[l][s_l] in position order times 1/L.
+// optimize/ga.py::ga_assign_reference is the bit-exact host twin.
+__device__ __forceinline__ bool ga_valid(const short* s, int L, const uint8_t* __restrict__ conflict) {
+  if (conflict)
+    for (int i = 0; i < L; ++i)
+      for (int j = i + 1; j < L; ++j)
+        if (s[i] == s[j] && conflict[(long long)i * L + j]) return false;
+  return true;
+}
+
+__device__ __forceinline__ float ga_price(const short* s, int L, int V, const float* __restrict__ cost,
+                                          const uint8_t* __restrict__ conflict, float invL, float invalid) {
+  float acc = 0.f;
+  for (int l = 0; l < L; ++l) acc += cost[(long long)l * V + s[l]];
+  return ga_valid(s, L, conflict) ? acc * invL : invalid;
+}
+
+__global__ __launch_bounds__(64) void ga_assign_kernel(
+    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, float invalid, int swap,
+    short* __restrict__ pop, float* __restrict__ pop_cost, float* __restrict__ hist, GaArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ga_lds[];
+  GaPool<short> W;
+  W.carve(ga_lds, A.P, L, A.r);
+  const int lane = threadIdx.x;
+  const unsigned long long gi = (unsigned long long)(A.island_base + (long long)blockIdx.x);
+  const float invL = 1.f / (float)L;
+  ga_island(W, A, L, pop, pop_cost, hist, lane, 64, [&](unsigned long long ctr0) {
+    short* c = W.kid + (size_t)lane * L;
+    if (lane < 2 * A.r) {
+      const int h = lane & 1;
+      const unsigned long long ctr = ctr0 + (unsigned long long)(lane >> 1);
+      const GaPair pr = ga_draw_pair(A.seed, ctr, gi, A.m, L);
+      const short* Hd = W.pa + (size_t)W.ord[h ? pr.b : pr.a] * L;  // head of this child
+      const short* Tl = W.pa + (size_t)W.ord[h ? pr.a : pr.b] * L;  // tail
+      for (int l = 0; l < L; ++l) c[l] = l < pr.x ? Hd[l] : Tl[l];
+      int pos = 0, old = 0, v = 0, holder = -1;
+      ga_mutate(
+          A, ctr, gi, h,
+          [&](unsigned qp, unsigned qv) {
+            pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+            old = c[pos];
+            v = min((int)(av::u32_to_unit(qv) * (float)(V - 1)), V - 2);
             v += v >= old;
-            int holder = -1;
+            holder = -1;
             if (swap)
               for (int j = 0; j < L; ++j)
                 if (j != pos && c[j] == v) { holder = j; break; }
             if (holder >= 0) c[holder] = (short)old;
             c[pos] = (short)v;
-            if (t == GA_MAX_TRY - 1 || ga_valid(c, L, conflict)) break;
+          },
+          [&] { return ga_valid(c, L, conflict); },
+          [&] {
             c[pos] = (short)old;
             if (holder >= 0) c[holder] = (short)v;
-          }
-        }
-      }
+          });
     }
     __syncthreads();
-    // 3. price the children
-    if (lane < 2 * r) kc[lane] = ga_price(kid + (size_t)lane * L, L, V, cost, conflict, invL, invalid);
-    __syncthreads();
-    ga_rank(kc, 2 * r, lane, kord);
-    __syncthreads();
-    // 4. replacement
-    ga_replace(pa, pb, kid, pc, pc2, kc, ord, kord, nsrc, P, L, r, purge_first, lane);
-    short* t = pa; pa = pb; pb = t;
-    float* tc = pc; pc = pc2; pc2 = tc;
-  }
-  for (int e = lane; e < P * L; e += 64) gpop[e] = pa[e];
-  if (lane < P) pop_cost[isl * P + lane] = pc[lane];
+    if (lane < 2 * A.r) W.kc[lane] = ga_price(c, L, V, cost, conflict, invL, invalid);
+  });
 }
 
 // ---- island GA over a meeting-schedule domain (P/app/mesched.py, optimize/domains.py) ----------
-// The frame of ga_assign_kernel (one wave per island, pools / children / costs in LDS for all G
-// generations, Philox by global island index) with the domain's own validity and cost:
+// The island frame above (one wave per island) with the domain's own validity and cost:
 //   * a solution is (day, hour, minute) index triples of M meetings, L = 3 M; meeting i starts at
 //     (days[d] - 1) 86400 + hours[h] 3600 + minutes[mi] 60 s and lasts dur[i] s;
 //   * invalid: two meetings with a common participant overlap, a meeting of a blocked person
@@ -290,16 +385,13 @@ __global__ __launch_bounds__(64) void ga_assign_kernel(
 //     36000 ndays - (total duration of q's meetings) and (meetings of q) + ndays, so no per-day
 //     counters are kept: one OR of day bits per person.  pc = 8 - (free / nslots) / 3600,
 //     cost = sum(pc w) / sum(w) in fp32 with q ascending, multiply and add rounded separately;
-//   * lane c < 2r builds, mutates and prices child c of pair c >> 1 — both lanes of a pair draw the
-//     same Philox word, the crossover cut falls between meetings, mutation moves one index to a
-//     different value of its table (tables of one value are left alone).
+//   * the crossover cut falls between meetings (3 x), mutation moves one index to a different value
+//     of its table (tables of one value are left alone).
 // Each child lane keeps the start second and the day bit of every meeting of its child in two
 // lane-private LDS rows (odd stride: conflict-free), so no private array is indexed dynamically.
 // optimize/ga_meeting.py::ga_meeting_reference is the bit-exact host twin.
 constexpr int MT_MAX_M = 32, MT_MAX_Q = 256, MT_MAX_CARD = 32, MT_MAX_LIST = 16;
 constexpr int MT_DOM_INTS = 3 * MT_MAX_CARD + 2 * MT_MAX_M + 2 * MT_MAX_Q + 5 * MT_MAX_LIST;  // staged domain
-
-__host__ __device__ constexpr size_t mt_a16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 struct MtLds {  // the staged domain
   const int *days, *hours, *minutes, *dur, *blocked, *ordered;
@@ -372,22 +464,13 @@ __device__ __forceinline__ float mt_cost(const MtLds& D, const unsigned* db) {
 
 __global__ __launch_bounds__(64) void ga_meeting_kernel(
     avk::GaMeetingDomain dom, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
-    float* __restrict__ hist, int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
-    long long island_base, unsigned long long gen_base) {
+    float* __restrict__ hist, GaArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gm_lds[];
   const int M = dom.M, L = 3 * M, Ms = M | 1;  // Ms: odd stride of the lane-private rows
-  unsigned char* cur = gm_lds;
-  short* pa = reinterpret_cast<short*>(cur);  cur += mt_a16((size_t)P * L * sizeof(short));      // [P][L] pool
-  short* pb = reinterpret_cast<short*>(cur);  cur += mt_a16((size_t)P * L * sizeof(short));      // [P][L] next pool
-  short* kid = reinterpret_cast<short*>(cur); cur += mt_a16((size_t)2 * r * L * sizeof(short));  // [2r][L] children
-  float* pc = reinterpret_cast<float*>(cur);  cur += mt_a16((size_t)P * sizeof(float));
-  float* pc2 = reinterpret_cast<float*>(cur); cur += mt_a16((size_t)P * sizeof(float));
-  float* kc = reinterpret_cast<float*>(cur);  cur += mt_a16((size_t)2 * r * sizeof(float));
-  int* ord = reinterpret_cast<int*>(cur);     cur += mt_a16((size_t)P * sizeof(int));
-  int* kord = reinterpret_cast<int*>(cur);    cur += mt_a16((size_t)2 * r * sizeof(int));
-  int* nsrc = reinterpret_cast<int*>(cur);    cur += mt_a16((size_t)P * sizeof(int));
-  int* st_all = reinterpret_cast<int*>(cur);  cur += mt_a16((size_t)2 * r * Ms * sizeof(int));   // [2r][Ms] starts
-  unsigned* db_all = reinterpret_cast<unsigned*>(cur); cur += mt_a16((size_t)2 * r * Ms * sizeof(int));  // day bits
+  GaPool<short> W;
+  unsigned char* cur = W.carve(gm_lds, A.P, L, A.r);
+  int* st_all = reinterpret_cast<int*>(cur);  cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));   // [2r][Ms] starts
+  unsigned* db_all = reinterpret_cast<unsigned*>(cur); cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));  // day bits
   int* di = reinterpret_cast<int*>(cur);      // the domain, MT_DOM_INTS dwords
   int* l_days = di;
   int* l_hours = l_days + MT_MAX_CARD;
@@ -400,8 +483,7 @@ __global__ __launch_bounds__(64) void ga_meeting_kernel(
   int* l_ordered = l_blocked + 3 * MT_MAX_LIST;
 
   const int lane = threadIdx.x;
-  const long long isl = blockIdx.x;
-  const unsigned long long gi = (unsigned long long)(island_base + isl);
+  const unsigned long long gi = (unsigned long long)(A.island_base + (long long)blockIdx.x);
   if (lane < dom.nd) l_days[lane] = dom.days[lane];
   if (lane < dom.nh) l_hours[lane] = dom.hours[lane];
   if (lane < dom.nm) l_minutes[lane] = dom.minutes[lane];
@@ -417,73 +499,45 @@ __global__ __launch_bounds__(64) void ga_meeting_kernel(
   if (lane < 2 * dom.no) l_ordered[lane] = dom.ordered[lane];
   const MtLds D{l_days, l_hours, l_minutes, l_dur, l_blocked, l_ordered, l_share, l_member, l_role,
                 M, dom.Q, dom.nb, dom.no};
-  short* gpop = pop + isl * P * L;
-  for (int e = lane; e < P * L; e += 64) pa[e] = gpop[e];
-  if (lane < P) pc[lane] = pop_cost[isl * P + lane];
-  __syncthreads();
-  for (int g = 0; g < G; ++g) {
-    // 1. rank
-    ga_rank(pc, P, lane, ord);
-    __syncthreads();
-    if (lane == 0) hist[isl * G + g] = pc[ord[0]];
-    // 2 + 3. lane c: child c of pair c >> 1, built, mutated and priced
-    if (lane < 2 * r) {
+  ga_island(W, A, L, pop, pop_cost, hist, lane, 64, [&](unsigned long long ctr0) {
+    if (lane < 2 * A.r) {
       const int h = lane & 1;
-      const unsigned long long ctr = 256ull * (gen_base + (unsigned long long)g) + (unsigned long long)(lane >> 1);
-      const av::u4 R = av::philox_draw(seed, ctr, gi);
-      const int a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
-      int b = 0;
-      if (m > 1) {
-        b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
-        b += b >= a;
-      }
-      const int cut = M > 1 ? 3 * (1 + min((int)(av::u32_to_unit(R.z) * (float)(M - 1)), M - 2)) : 0;
-      const short* A = pa + (size_t)ord[h ? b : a] * L;  // head of this child
-      const short* B = pa + (size_t)ord[h ? a : b] * L;  // tail
-      short* c = kid + (size_t)lane * L;
+      const unsigned long long ctr = ctr0 + (unsigned long long)(lane >> 1);
+      const GaPair pr = ga_draw_pair(A.seed, ctr, gi, A.m, M);
+      const int cut = 3 * pr.x;
+      const short* Hd = W.pa + (size_t)W.ord[h ? pr.b : pr.a] * L;  // head of this child
+      const short* Tl = W.pa + (size_t)W.ord[h ? pr.a : pr.b] * L;  // tail
+      short* c = W.kid + (size_t)lane * L;
       int* st = st_all + lane * Ms;
       unsigned* db = db_all + lane * Ms;
-      for (int l = 0; l < L; ++l) c[l] = l < cut ? A[l] : B[l];
+      for (int l = 0; l < L; ++l) c[l] = l < cut ? Hd[l] : Tl[l];
       for (int i = 0; i < M; ++i) mt_place(D, c, i, st, db);
-      bool ok;
-      if (mutate) {
-        // one index to a different value of its table, redrawn up to GA_MAX_TRY times until the
-        // child is valid; the last attempt stays otherwise
-        for (int t = 0;; ++t) {
-          const av::u4 Q = av::philox_draw(seed ^ 0xD1B54A32D192ED03ull, ctr * 16ull + (unsigned long long)t, gi);
-          const unsigned qp = h == 0 ? Q.x : Q.z, qv = h == 0 ? Q.y : Q.w;
-          const int pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
-          const int mi = pos / 3, comp = pos - 3 * mi;
-          const int card = comp == 0 ? dom.nd : comp == 1 ? dom.nh : dom.nm;
-          const int old = c[pos];
-          if (card > 1) {
-            int v = min((int)(av::u32_to_unit(qv) * (float)(card - 1)), card - 2);
-            v += v >= old;
-            c[pos] = (short)v;
-            mt_place(D, c, mi, st, db);
-          }
-          ok = mt_valid(D, st);
-          if (ok || t == GA_MAX_TRY - 1) break;
-          if (card > 1) {
-            c[pos] = (short)old;
-            mt_place(D, c, mi, st, db);
-          }
-        }
-      } else {
-        ok = mt_valid(D, st);
-      }
-      kc[lane] = ok ? mt_cost(D, db) : invalid;
+      int pos = 0, mi = 0, card = 0, old = 0;
+      const bool ok = ga_mutate(
+          A, ctr, gi, h,
+          [&](unsigned qp, unsigned qv) {
+            pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+            mi = pos / 3;
+            const int comp = pos - 3 * mi;
+            card = comp == 0 ? dom.nd : comp == 1 ? dom.nh : dom.nm;
+            old = c[pos];
+            if (card > 1) {
+              int v = min((int)(av::u32_to_unit(qv) * (float)(card - 1)), card - 2);
+              v += v >= old;
+              c[pos] = (short)v;
+              mt_place(D, c, mi, st, db);
+            }
+          },
+          [&] { return mt_valid(D, st); },
+          [&] {
+            if (card > 1) {
+              c[pos] = (short)old;
+              mt_place(D, c, mi, st, db);
+            }
+          });
+      W.kc[lane] = ok ? mt_cost(D, db) : invalid;
     }
-    __syncthreads();
-    ga_rank(kc, 2 * r, lane, kord);
-    __syncthreads();
-    // 4. replacement
-    ga_replace(pa, pb, kid, pc, pc2, kc, ord, kord, nsrc, P, L, r, purge_first, lane);
-    short* t = pa; pa = pb; pb = t;
-    float* tc = pc; pc = pc2; pc2 = tc;
-  }
-  for (int e = lane; e < P * L; e += 64) gpop[e] = pa[e];
-  if (lane < P) pop_cost[isl * P + lane] = pc[lane];
+  });
 }
 
 // ---- feature subsets scored by naive Bayes (P/app/fesel.py, optimize/domains.py) ---------------
@@ -655,13 +709,12 @@ __global__ __launch_bounds__(256) void subset_errors_kernel(
 }
 
 // ---- island GA over feature subsets ------------------------------------------------------------
-// The frame of ga_meeting_kernel (pools, children and costs in LDS for all G generations, Philox by
-// global island index, lane c < 2r of wave 0 builds and mutates child c of pair c >> 1 from the same
-// Philox words), with a solution held as one 32-bit mask:
-//   * valid: min_size <= popcount <= max_size; mutation flips one bit (the value draw of the
-//     shared counter layout is unused), redrawn up to GA_MAX_TRY times until the child is valid;
+// The island frame above with a solution held as one 32-bit mask; wave 0 breeds (lane c < 2r, child
+// c), then every wave of the workgroup scores:
+//   * valid: min_size <= popcount <= max_size; mutation flips one bit (the value word of the
+//     shared counter layout is unused);
 //   * the crossover cut lies in [1, F) (none at F = 1);
-//   * cost: every wave of the workgroup then scores the valid children over the N rows, tile by
+//   * cost: every wave of the workgroup scores the valid children over the N rows, tile by
 //     tile, into integer LDS counters; cost = (float)errors / (float)N, `invalid` for an invalid child.
 // pop stays int16 [islands][P][F] of 0 / 1 at the interface; it is packed on entry and unpacked
 // on exit.  The workgroup has blockDim.x = 256 or 1,024 threads; no result depends on it.
@@ -669,65 +722,41 @@ __global__ __launch_bounds__(256) void subset_errors_kernel(
 __global__ __launch_bounds__(1024) void ga_subset_kernel(
     const float* __restrict__ LL, const float* __restrict__ log_prior, const int* __restrict__ labels, int N, int F,
     int C, int min_size, int max_size, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
-    float* __restrict__ hist, int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
-    long long island_base, unsigned long long gen_base, int TR) {
+    float* __restrict__ hist, GaArgs A, int TR) {
   extern __shared__ __attribute__((aligned(16))) float fs_tile[];
   __shared__ unsigned s_pool[2][64], s_kid[64];
   __shared__ float s_pc[2][64], s_kc[64], s_prior[FS_MAX_C];
   __shared__ int s_ord[64], s_kord[64], s_nsrc[64], s_cnt[64], s_vk[64], s_nv;
-  unsigned *pa = s_pool[0], *pb = s_pool[1];
-  float *pc = s_pc[0], *pc2 = s_pc[1];
+  GaPool<unsigned> W{s_pool[0], s_pool[1], s_kid, s_pc[0], s_pc[1], s_kc, s_ord, s_kord, s_nsrc};
   const int tid = threadIdx.x, nt = blockDim.x, FC = F * C, stride = FC | 1;
   const unsigned magic = 0xFFFFFFFFu / (unsigned)FC + 1u;
   const int ntiles = (N + TR - 1) / TR;
-  const long long isl = blockIdx.x;
-  const unsigned long long gi = (unsigned long long)(island_base + isl);
-  short* gpop = pop + isl * P * F;
-  if (tid < P) {
-    unsigned mk = 0;
-    for (int f = 0; f < F; ++f) mk |= (unsigned)(gpop[tid * F + f] != 0) << f;
-    pa[tid] = mk;
-    pc[tid] = pop_cost[isl * P + tid];
-  }
+  const unsigned long long gi = (unsigned long long)(A.island_base + (long long)blockIdx.x);
   if (tid < C) s_prior[tid] = log_prior[tid];
   bool staged = false;
-  __syncthreads();
-  for (int g = 0; g < G; ++g) {
-    // 1. rank
-    ga_rank(pc, P, tid, s_ord);
-    __syncthreads();
-    if (tid == 0) hist[isl * G + g] = pc[s_ord[0]];
-    // 2. wave 0: lane c builds and mutates child c of pair c >> 1; the valid children are listed in s_vk
+  ga_island(W, A, F, pop, pop_cost, hist, tid, nt, [&](unsigned long long ctr0) {
+    // wave 0: lane c builds and mutates child c of pair c >> 1; the valid children are listed in s_vk
     bool ok = false;
     if (tid < 64) {
-      if (tid < 2 * r) {
+      if (tid < 2 * A.r) {
         const int h = tid & 1;
-        const unsigned long long ctr = 256ull * (gen_base + (unsigned long long)g) + (unsigned long long)(tid >> 1);
-        const av::u4 R = av::philox_draw(seed, ctr, gi);
-        const int a = min((int)(av::u32_to_unit(R.x) * (float)m), m - 1);
-        int b = 0;
-        if (m > 1) {
-          b = min((int)(av::u32_to_unit(R.y) * (float)(m - 1)), m - 2);
-          b += b >= a;
-        }
-        const int cut = F > 1 ? 1 + min((int)(av::u32_to_unit(R.z) * (float)(F - 1)), F - 2) : 0;
-        const unsigned low = (1u << cut) - 1u;  // cut <= 31
-        const unsigned A = pa[s_ord[h ? b : a]], Bm = pa[s_ord[h ? a : b]];  // head, tail
-        unsigned c = (A & low) | (Bm & ~low);
-        if (mutate) {
-          for (int t = 0;; ++t) {
-            const av::u4 Q = av::philox_draw(seed ^ 0xD1B54A32D192ED03ull, ctr * 16ull + (unsigned long long)t, gi);
-            const int pos = min((int)(av::u32_to_unit(h == 0 ? Q.x : Q.z) * (float)F), F - 1);
-            c ^= 1u << pos;
-            const int sz = __popc(c);
-            ok = sz >= min_size && sz <= max_size;
-            if (ok || t == GA_MAX_TRY - 1) break;
-            c ^= 1u << pos;
-          }
-        } else {
-          const int sz = __popc(c);
-          ok = sz >= min_size && sz <= max_size;
-        }
+        const unsigned long long ctr = ctr0 + (unsigned long long)(tid >> 1);
+        const GaPair pr = ga_draw_pair(A.seed, ctr, gi, A.m, F);
+        const unsigned low = (1u << pr.x) - 1u;  // cut <= 31
+        const unsigned Hd = W.pa[W.ord[h ? pr.b : pr.a]], Tl = W.pa[W.ord[h ? pr.a : pr.b]];  // head, tail
+        unsigned c = (Hd & low) | (Tl & ~low);
+        int pos = 0;
+        ok = ga_mutate(
+            A, ctr, gi, h,
+            [&](unsigned qp, unsigned) {
+              pos = min((int)(av::u32_to_unit(qp) * (float)F), F - 1);
+              c ^= 1u << pos;
+            },
+            [&] {
+              const int sz = __popc(c);
+              return sz >= min_size && sz <= max_size;
+            },
+            [&] { c ^= 1u << pos; });
         s_kid[tid] = c;
         s_kc[tid] = invalid;
         s_cnt[tid] = 0;
@@ -737,7 +766,7 @@ __global__ __launch_bounds__(1024) void ga_subset_kernel(
       if (tid == 0) s_nv = __popcll(vb);
     }
     __syncthreads();
-    // 3. all waves: the valid children over the N rows
+    // all waves: the valid children over the N rows
     const int nv = s_nv;
     if (nv)
       for (int t = 0; t < ntiles; ++t) {
@@ -752,49 +781,40 @@ __global__ __launch_bounds__(1024) void ga_subset_kernel(
         __syncthreads();
       }
     if (ok) s_kc[tid] = (float)s_cnt[tid] / (float)N;
-    __syncthreads();
-    ga_rank(s_kc, 2 * r, tid, s_kord);
-    __syncthreads();
-    // 4. replacement
-    ga_replace(pa, pb, s_kid, pc, pc2, s_kc, s_ord, s_kord, s_nsrc, P, 1, r, purge_first, tid, nt);
-    unsigned* tp = pa; pa = pb; pb = tp;
-    float* tc = pc; pc = pc2; pc2 = tc;
-  }
-  for (int e = tid; e < P * F; e += nt) {
-    const int p = e / F;
-    gpop[e] = (short)((pa[p] >> (e - p * F)) & 1u);
-  }
-  if (tid < P) pop_cost[isl * P + tid] = pc[tid];
+  });
 }
 
 }  // namespace
 
 namespace avk {
 
-size_t ga_assign_lds(int P, int L, int r) {
-  return (size_t)(2 * P + 2 * r) * L * sizeof(short) + (size_t)(2 * P + 2 * r) * sizeof(float) +
-         (size_t)(2 * P + 2 * r) * sizeof(int);
+// one lane per member, per child and, when the children join the pool, per candidate
+void ga_check_pool(const char* who, long long P, long long m, long long r, bool purge_first) {
+  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P)
+    throw std::invalid_argument(std::string(who) + ": 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
+  if (!purge_first && P + r > 64)
+    throw std::invalid_argument(std::string(who) + ": P + r <= 64 when children join the pool");
 }
+
+size_t ga_assign_lds(int P, int L, int r) { return GaPool<short>::bytes(P, L, r); }
 
 void ga_assign(const float* cost, int L, int V, const uint8_t* conflict, float invalid, short* pop, float* pop_cost,
                float* hist, int islands, int P, int G, int m, int r, int purge_first, int mutate, int swap,
-               unsigned long long seed, long long island_base, int gen_base, hipStream_t stream) {
+               unsigned long long seed, long long island_base, unsigned long long gen_base, hipStream_t stream) {
   if (islands <= 0 || G <= 0) return;
-  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P || L < 1 || V < 2)
-    throw std::invalid_argument("ga_assign: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P, L >= 1, V >= 2");
-  if (!purge_first && P + r > 64) throw std::invalid_argument("ga_assign: P + r <= 64 when children join the pool");
+  if (L < 1 || V < 2) throw std::invalid_argument("ga_assign: L >= 1, V >= 2");
+  ga_check_pool("ga_assign", P, m, r, purge_first);
   const size_t lds = ga_assign_lds(P, L, r);
   if (lds > 64 * 1024) throw std::invalid_argument("ga_assign: pool, children and costs exceed 64 KiB of LDS");
-  ga_assign_kernel<<<islands, 64, lds, stream>>>(cost, L, V, conflict, invalid, pop, pop_cost, hist, P, G, m, r,
-                                                 purge_first, mutate, swap, seed, island_base, gen_base);
+  ga_assign_kernel<<<islands, 64, lds, stream>>>(cost, L, V, conflict, invalid, swap, pop, pop_cost, hist,
+                                                 GaArgs{P, G, m, r, purge_first, mutate, seed, island_base, gen_base});
   AV_HIP_CHECK(hipGetLastError());
 }
 
 size_t ga_meeting_lds(int P, int L, int r) {
   const size_t Ms = (size_t)(L / 3) | 1;
-  return 2 * mt_a16((size_t)P * L * sizeof(short)) + mt_a16((size_t)2 * r * L * sizeof(short)) +
-         4 * mt_a16((size_t)P * 4) + 2 * mt_a16((size_t)2 * r * 4) +  // pc, pc2, ord, nsrc; kc, kord
-         2 * mt_a16((size_t)2 * r * Ms * sizeof(int)) + mt_a16((size_t)MT_DOM_INTS * sizeof(int));
+  return GaPool<short>::bytes(P, L, r) + 2 * ga_a16((size_t)2 * r * Ms * sizeof(int)) +
+         ga_a16((size_t)MT_DOM_INTS * sizeof(int));
 }
 
 void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* pop_cost, float* hist, int islands,
@@ -806,14 +826,12 @@ void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* po
     throw std::invalid_argument("ga_meeting: value tables of 1..32 entries");
   if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
     throw std::invalid_argument("ga_meeting: at most 16 blocked entries and 16 ordered pairs");
-  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P)
-    throw std::invalid_argument("ga_meeting: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
-  if (!purge_first && P + r > 64) throw std::invalid_argument("ga_meeting: P + r <= 64 when children join the pool");
+  ga_check_pool("ga_meeting", P, m, r, purge_first);
   const size_t lds = ga_meeting_lds(P, 3 * dom.M, r);
   if (lds > 64 * 1024) throw std::invalid_argument("ga_meeting: pool, children and costs exceed 64 KiB of LDS");
   if (islands <= 0 || G <= 0) return;
-  ga_meeting_kernel<<<islands, 64, lds, stream>>>(dom, invalid, pop, pop_cost, hist, P, G, m, r, purge_first, mutate,
-                                                  seed, island_base, gen_base);
+  ga_meeting_kernel<<<islands, 64, lds, stream>>>(dom, invalid, pop, pop_cost, hist,
+                                                  GaArgs{P, G, m, r, purge_first, mutate, seed, island_base, gen_base});
   AV_HIP_CHECK(hipGetLastError());
 }
 
@@ -850,15 +868,13 @@ void ga_subset(const float* LL, const float* log_prior, const int* labels, int N
                int r, int purge_first, int mutate, unsigned long long seed, long long island_base,
                unsigned long long gen_base, hipStream_t stream) {
   fs_check(N, F, C, "ga_subset");
-  if (P < 2 || P > 64 || r < 1 || 2 * r > 64 || r > P || m < 1 || m > P)
-    throw std::invalid_argument("ga_subset: 2 <= P <= 64, 1 <= r <= min(P, 32), 1 <= m <= P");
-  if (!purge_first && P + r > 64) throw std::invalid_argument("ga_subset: P + r <= 64 when children join the pool");
+  ga_check_pool("ga_subset", P, m, r, purge_first);
   if (islands <= 0 || G <= 0) return;
   const int FC = F * C, nt = ga_subset_threads(N), TR = fs_tile_rows(FC, nt);
   const size_t lds = (size_t)TR * (FC | 1) * sizeof(float);
   ga_subset_kernel<<<islands, nt, lds, stream>>>(LL, log_prior, labels, N, F, C, min_size, max_size, invalid, pop,
-                                                 pop_cost, hist, P, G, m, r, purge_first, mutate, seed, island_base,
-                                                 gen_base, TR);
+                                                 pop_cost, hist,
+                                                 GaArgs{P, G, m, r, purge_first, mutate, seed, island_base, gen_base}, TR);
   AV_HIP_CHECK(hipGetLastError());
 }
 

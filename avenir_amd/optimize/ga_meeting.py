@@ -20,8 +20,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ..ops.random import philox4x32, u32_to_unit
-from .ga import _INIT_KEY, _MAX_TRY, _MUT_KEY, _unit_index
+from ..ops.random import u32_to_unit
+from .ga import (GaDomain, _set, _unit_index, ga_assign_lds, ga_islands_launch, ga_islands_reference, ga_redraw_init,
+                 splice)
 
 MAX_M, MAX_Q, MAX_CARD, MAX_LIST = 32, 256, 32, 16      # the kernel's limits
 _TIME_LIMIT = 1 << 24                                     # seconds: exact in int32 and in fp32
@@ -29,11 +30,11 @@ _F = np.float32
 
 
 def ga_meeting_lds(P: int, L: int, r: int) -> int:
-    """Bytes of LDS per island (``avk::ga_meeting_lds``): pools, children, costs, orders, the children's
+    """Bytes of LDS per island (``avk::ga_meeting_lds``): the pool view of the frame, the children's
     start / day-bit rows and the staged domain, every array rounded up to 16 bytes."""
     a16 = lambda n: (n + 15) & ~15
     ms = (L // 3) | 1
-    return (2 * a16(2 * P * L) + a16(4 * r * L) + 4 * a16(4 * P) + 2 * a16(8 * r) + 2 * a16(8 * r * ms)
+    return (ga_assign_lds(P, L, r) + 2 * a16(8 * r * ms)
             + a16(4 * (3 * MAX_CARD + 2 * MAX_M + 2 * MAX_Q + 5 * MAX_LIST)))
 
 
@@ -155,27 +156,10 @@ def ga_meeting_price(tables: dict, sol: np.ndarray) -> np.ndarray:
 
 
 def ga_meeting_init(tables: dict, n_islands: int, P: int, seed: int, island_base: int, max_try: int = 40) -> np.ndarray:
-    """Initial pools [islands, P, 3 M] int16, host-side per global island: member p of island gi,
-    attempt a, position l is min((int)(u card_l), card_l - 1) with u from
-    Philox(seed ^ INIT, (p L + l) 64 + a, gi).x; the whole member is redrawn while it is invalid (up
-    to ``max_try`` <= 64 attempts, the last one stays)."""
-    if not 1 <= max_try <= 64:
-        raise ValueError("max_try must lie in [1, 64]")
-    L, cards = tables["L"], tables["cards"]
-    out = np.zeros((n_islands, P, L), dtype=np.int64)
-    ti, tp = (x.reshape(-1) for x in np.meshgrid(np.arange(n_islands), np.arange(P), indexing="ij"))
-    pos = np.arange(L, dtype=np.uint64)[None, :]
-    for a in range(max_try):
-        if ti.size == 0:
-            break
-        off = (tp.astype(np.uint64)[:, None] * np.uint64(L) + pos) * np.uint64(64) + np.uint64(a)
-        gis = np.broadcast_to((ti + island_base).astype(np.uint64)[:, None], off.shape)
-        x, _, _, _ = philox4x32(seed ^ _INIT_KEY, off, gis)
-        draw = np.minimum((u32_to_unit(x) * cards.astype(np.float32)[None, :]).astype(np.int64), cards[None, :] - 1)
-        out[ti, tp] = draw
-        bad = ~ga_meeting_valid(tables, draw)
-        ti, tp = ti[bad], tp[bad]
-    return out.astype(np.int16)
+    """Initial pools [islands, P, 3 M] int16: :func:`~avenir_amd.optimize.ga.ga_redraw_init` over the
+    value tables' sizes, a member redrawn while it is no valid schedule."""
+    return ga_redraw_init(tables["cards"], lambda s: ga_meeting_valid(tables, s), n_islands, P, seed, island_base,
+                          max_try)
 
 
 def ga_meeting_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
@@ -183,67 +167,23 @@ def ga_meeting_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G:
                          gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Host twin of ``ga_meeting_kernel`` (all islands at once).  Returns (pop int16, cost float32,
     hist float32)."""
-    pop = np.array(pop, dtype=np.int64)
-    pc = np.array(pop_cost, dtype=np.float32)
-    I, P, L = pop.shape
-    M, cards = tables["M"], tables["cards"]
-    gis = np.arange(island_base, island_base + I, dtype=np.uint64)
-    ar = np.arange(I)
-    ii = ar[:, None]
-    kk = np.arange(r)[None, :]
-    gir = np.broadcast_to(gis[:, None], (I, r))
-    hist = np.zeros((I, G), dtype=np.float32)
-    for g in range(G):
-        ord_ = np.argsort(pc, axis=1, kind="stable")
-        hist[:, g] = pc[ar, ord_[:, 0]]
-        # all r pairs of all islands at once: arrays [I, r]
-        ctr = np.array([256 * (gen_base + g) + k for k in range(r)], dtype=np.uint64)[None, :]
-        x_, y_, z_, _ = philox4x32(seed, np.broadcast_to(ctr, (I, r)), gir)
-        a = _unit_index(u32_to_unit(x_), m)
-        b = np.zeros((I, r), dtype=np.int64)
-        if m > 1:
-            b = np.minimum((u32_to_unit(y_) * _F(m - 1)).astype(np.int64), m - 2)
-            b = b + (b >= a)
-        cut = np.zeros((I, r), dtype=np.int64)
-        if M > 1:                                                # the cut falls between two meetings
-            cut = 3 * (1 + np.minimum((u32_to_unit(z_) * _F(M - 1)).astype(np.int64), M - 2))
-        A = pop[ii, ord_[ii, a]]                                 # [I, r, L]
-        B = pop[ii, ord_[ii, b]]
-        left = np.arange(L)[None, None, :] < cut[:, :, None]
-        pair = [np.where(left, A, B), np.where(left, B, A)]
-        if mutate:
-            for h, c in enumerate(pair):
-                done = np.zeros((I, r), dtype=bool)
-                for t in range(_MAX_TRY):
-                    if done.all():
-                        break
-                    q = philox4x32(seed ^ _MUT_KEY, np.broadcast_to(ctr * np.uint64(16) + np.uint64(t), (I, r)), gir)
-                    qp, qv = (q[0], q[1]) if h == 0 else (q[2], q[3])
-                    pos = _unit_index(u32_to_unit(qp), L)
-                    old = c[ii, kk, pos]
-                    card = cards[pos]
-                    v = np.minimum((u32_to_unit(qv) * np.maximum(card - 1, 1).astype(np.float32)).astype(np.int64),
-                                   np.maximum(card - 2, 0))
-                    v = np.where(card > 1, v + (v >= old), old)          # a one-value table keeps its value
-                    cand = c.copy()
-                    cand[ii, kk, pos] = v
-                    take = ~done & ((t == _MAX_TRY - 1) | ga_meeting_valid(tables, cand))
-                    c[take] = cand[take]
-                    done |= take
-        kids = np.stack(pair, axis=2).reshape(I, 2 * r, L)           # child 2k, 2k + 1 of pair k
-        kc = ga_meeting_price(tables, kids)
-        kord = np.argsort(kc, axis=1, kind="stable")
-        if purge_first:
-            nsrc = np.concatenate([ord_[:, : P - r], P + kord[:, :r]], axis=1)
-        else:
-            src = np.concatenate([np.broadcast_to(np.arange(P), (I, P)), P + kord[:, :r]], axis=1)
-            cc = np.concatenate([pc, kc[ii, kord[:, :r]]], axis=1)
-            nsrc = np.take_along_axis(src, np.argsort(cc, axis=1, kind="stable")[:, :P], axis=1)
-        allp = np.concatenate([pop, kids], axis=1)
-        allc = np.concatenate([pc, kc], axis=1)
-        pop = allp[ii, nsrc]
-        pc = allc[ii, nsrc]
-    return pop.astype(np.int16), pc, hist
+    L, cards = tables["L"], tables["cards"]
+
+    def mutated(c, qp, qv):
+        pos = _unit_index(u32_to_unit(qp), L)
+        old = np.take_along_axis(c, pos[..., None], axis=-1)[..., 0]
+        card = cards[pos]
+        v = np.minimum((u32_to_unit(qv) * np.maximum(card - 1, 1).astype(np.float32)).astype(np.int64),
+                       np.maximum(card - 2, 0))
+        cand = c.copy()
+        _set(cand, pos, np.where(card > 1, v + (v >= old), old))         # a one-value table keeps its value
+        return cand
+
+    # the cut falls between two meetings
+    dom = GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16),
+                   ncut=tables["M"], scale=3, crossover=splice, mutated=mutated,
+                   valid=lambda c: ga_meeting_valid(tables, c), price=lambda kids: ga_meeting_price(tables, kids))
+    return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
 
 
 _DEV_KEYS = ("days", "hours", "minutes", "dur", "share", "member", "role_w", "blocked", "ordered")
@@ -268,10 +208,7 @@ def ga_meeting_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int
     device = torch.device(device)
     if device.type == "cuda":
         from .. import _native
-        tp = torch.from_numpy(np.ascontiguousarray(pop, dtype=np.int16)).to(device)
-        tc = torch.from_numpy(np.ascontiguousarray(pop_cost, dtype=np.float32)).to(device)
-        hist = torch.empty((pop.shape[0], G), dtype=torch.float32, device=device)
-        _native.C().ga_meeting(*_device_tables(tables, device), float(tables["invalid"]), tp, tc, hist, G, m, r,
-                               bool(purge_first), bool(mutate), int(seed), int(island_base), int(gen_base))
-        return tp.cpu().numpy(), tc.cpu().numpy(), hist.cpu().numpy()
+        head = (*_device_tables(tables, device), float(tables["invalid"]))
+        return ga_islands_launch(_native.C().ga_meeting, head, pop, pop_cost, G, m, r, purge_first, mutate, seed,
+                                 island_base, gen_base, device)
     return ga_meeting_reference(tables, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)

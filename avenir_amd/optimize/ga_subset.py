@@ -26,8 +26,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ..ops.random import philox4x32, u32_to_unit
-from .ga import _INIT_KEY, _MAX_TRY, _MUT_KEY, _unit_index
+from ..ops.random import u32_to_unit
+from .ga import GaDomain, _unit_index, ga_islands_launch, ga_islands_reference, ga_redraw_init
 
 MAX_F, MAX_C, MAX_N = 32, 16, 1 << 24                   # the kernels' limits: F <= 32, C <= 16, N < 2^24
 # GeneticAlgorithm takes the island engine up to this many rows (search._island_engine): the largest
@@ -189,26 +189,10 @@ def ga_subset_price(tables: dict, masks, device="cpu") -> np.ndarray:
 
 
 def ga_subset_init(tables: dict, n_islands: int, P: int, seed: int, island_base: int, max_try: int = 40) -> np.ndarray:
-    """Initial pools [islands, P, F] int16 of 0 / 1, host-side per global island: member p of island
-    gi, attempt a, position l is min((int)(2 u), 1) with u from Philox(seed ^ INIT, (p F + l) 64 + a, gi).x;
-    the whole member is redrawn while it is invalid (up to ``max_try`` <= 64 attempts, the last one stays)."""
-    if not 1 <= max_try <= 64:
-        raise ValueError("max_try must lie in [1, 64]")
-    L = tables["F"]
-    out = np.zeros((n_islands, P, L), dtype=np.int64)
-    ti, tp = (x.reshape(-1) for x in np.meshgrid(np.arange(n_islands), np.arange(P), indexing="ij"))
-    pos = np.arange(L, dtype=np.uint64)[None, :]
-    for a in range(max_try):
-        if ti.size == 0:
-            break
-        off = (tp.astype(np.uint64)[:, None] * np.uint64(L) + pos) * np.uint64(64) + np.uint64(a)
-        gis = np.broadcast_to((ti + island_base).astype(np.uint64)[:, None], off.shape)
-        x, _, _, _ = philox4x32(seed ^ _INIT_KEY, off, gis)
-        draw = _unit_index(u32_to_unit(x), 2)
-        out[ti, tp] = draw
-        bad = ~ga_subset_valid(tables, pack_masks(draw))
-        ti, tp = ti[bad], tp[bad]
-    return out.astype(np.int16)
+    """Initial pools [islands, P, F] int16 of 0 / 1: :func:`~avenir_amd.optimize.ga.ga_redraw_init`
+    with two values per position, a member redrawn while its size is out of range."""
+    return ga_redraw_init(np.full(tables["F"], 2, dtype=np.int64), lambda s: ga_subset_valid(tables, pack_masks(s)),
+                          n_islands, P, seed, island_base, max_try)
 
 
 def ga_subset_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
@@ -217,55 +201,18 @@ def ga_subset_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: 
     """Host twin of ``ga_subset_kernel`` (all islands at once).  Returns (pop int16, cost float32,
     hist float32)."""
     F = tables["F"]
-    mk = pack_masks(pop)                                             # [I, P] uint32
-    pc = np.array(pop_cost, dtype=np.float32)
-    I, P = mk.shape
-    gis = np.arange(island_base, island_base + I, dtype=np.uint64)
-    ar = np.arange(I)
-    ii = ar[:, None]
-    gir = np.broadcast_to(gis[:, None], (I, r))
-    hist = np.zeros((I, G), dtype=np.float32)
-    for g in range(G):
-        ord_ = np.argsort(pc, axis=1, kind="stable")
-        hist[:, g] = pc[ar, ord_[:, 0]]
-        ctr = np.array([256 * (gen_base + g) + k for k in range(r)], dtype=np.uint64)[None, :]
-        x_, y_, z_, _ = philox4x32(seed, np.broadcast_to(ctr, (I, r)), gir)
-        a = _unit_index(u32_to_unit(x_), m)
-        b = np.zeros((I, r), dtype=np.int64)
-        if m > 1:
-            b = np.minimum((u32_to_unit(y_) * _F(m - 1)).astype(np.int64), m - 2)
-            b = b + (b >= a)
-        cut = np.zeros((I, r), dtype=np.int64)
-        if F > 1:
-            cut = 1 + np.minimum((u32_to_unit(z_) * _F(F - 1)).astype(np.int64), F - 2)
+
+    def crossover(A, B, cut):
         low = ((np.uint64(1) << cut.astype(np.uint64)) - np.uint64(1)).astype(np.uint32)      # cut <= 31
-        A = mk[ii, ord_[ii, a]]                                      # [I, r]
-        B = mk[ii, ord_[ii, b]]
-        pair = [(A & low) | (B & ~low), (B & low) | (A & ~low)]
-        if mutate:
-            for h, c in enumerate(pair):
-                done = np.zeros((I, r), dtype=bool)
-                for t in range(_MAX_TRY):
-                    if done.all():
-                        break
-                    q = philox4x32(seed ^ _MUT_KEY, np.broadcast_to(ctr * np.uint64(16) + np.uint64(t), (I, r)), gir)
-                    pos = _unit_index(u32_to_unit(q[0] if h == 0 else q[2]), F)     # the value draw is unused:
-                    cand = c ^ (np.uint32(1) << pos.astype(np.uint32))              # a 0 / 1 position flips
-                    take = ~done & ((t == _MAX_TRY - 1) | ga_subset_valid(tables, cand))
-                    c[take] = cand[take]
-                    done |= take
-        kids = np.stack(pair, axis=2).reshape(I, 2 * r)              # child 2k, 2k + 1 of pair k
-        kc = ga_subset_price(tables, kids)
-        kord = np.argsort(kc, axis=1, kind="stable")
-        if purge_first:
-            nsrc = np.concatenate([ord_[:, : P - r], P + kord[:, :r]], axis=1)
-        else:
-            src = np.concatenate([np.broadcast_to(np.arange(P), (I, P)), P + kord[:, :r]], axis=1)
-            cc = np.concatenate([pc, kc[ii, kord[:, :r]]], axis=1)
-            nsrc = np.take_along_axis(src, np.argsort(cc, axis=1, kind="stable")[:, :P], axis=1)
-        mk = np.concatenate([mk, kids], axis=1)[ii, nsrc]
-        pc = np.concatenate([pc, kc], axis=1)[ii, nsrc]
-    return unpack_masks(mk, F), pc, hist
+        return (A & low) | (B & ~low), (B & low) | (A & ~low)
+
+    def mutated(c, qp, qv):                      # the value draw is unused: a 0 / 1 position flips
+        return c ^ (np.uint32(1) << _unit_index(u32_to_unit(qp), F).astype(np.uint32))
+
+    dom = GaDomain(encode=pack_masks, decode=lambda mk: unpack_masks(mk, F), ncut=F, scale=1, crossover=crossover,
+                   mutated=mutated, valid=lambda c: ga_subset_valid(tables, c),
+                   price=lambda kids: ga_subset_price(tables, kids))
+    return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
 
 
 def ga_subset_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool,
@@ -284,11 +231,7 @@ def ga_subset_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int,
     device = torch.device(device)
     if device.type == "cuda":
         from .. import _native
-        tp = torch.from_numpy(pop).to(device)
-        tc = torch.from_numpy(np.ascontiguousarray(pop_cost, dtype=np.float32)).to(device)
-        hist = torch.empty((pop.shape[0], G), dtype=torch.float32, device=device)
-        _native.C().ga_subset(*_device_tables(tables, device), tables["min_size"], tables["max_size"],
-                              float(tables["invalid"]), tp, tc, hist, G, m, r, bool(purge_first), bool(mutate),
-                              int(seed), int(island_base), int(gen_base))
-        return tp.cpu().numpy(), tc.cpu().numpy(), hist.cpu().numpy()
+        head = (*_device_tables(tables, device), tables["min_size"], tables["max_size"], float(tables["invalid"]))
+        return ga_islands_launch(_native.C().ga_subset, head, pop, pop_cost, G, m, r, purge_first, mutate, seed,
+                                 island_base, gen_base, device)
     return ga_subset_reference(tables, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)

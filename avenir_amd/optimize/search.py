@@ -388,71 +388,17 @@ def local_trajectory(d: SearchDomain, sols: torch.Tensor, costs: torch.Tensor, n
 # ================================================================================================
 # population optimisers
 # ================================================================================================
-class _AssignIslands:
-    """Island engine of an AssignmentDomain: ``ga_assign_kernel`` / its twin (optimize/ga.py)."""
+class _Islands:
+    """An island engine: one of the island kernels of optim.hip on a GPU, its host twin on the CPU.
+    ``names`` are the (GPU, CPU) engine names of ``OptResult.stats``; ``init(n, P, seed, island_base)``
+    returns the initial pools and costs; ``run(pop, cost, G, m, r, purge_first, mutate, seed,
+    island_base, device, gen_base=)`` advances them."""
 
-    def __init__(self, domain):
-        self.d = domain
-
-    def name(self, device) -> str:
-        return "ga_assign_kernel" if device.type == "cuda" else "ga_twin"
-
-    def init(self, n: int, P: int, seed: int, island_base: int):
-        from .ga import ga_init_population, ga_price
-        d = self.d
-        conf = None
-        if d.conflict is not None:
-            c = d.conflict.cpu().numpy()
-            conf = np.triu(c, 1) | np.triu(c, 1).T
-        pop = ga_init_population(n, P, d.L, d.V, seed, island_base, conf)
-        cost = ga_price(d.cost_table.cpu().numpy().astype(np.float32), conf, d.invalid_cost, pop.astype(np.int64))
-        return pop, cost
-
-    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
-        from .ga import ga_assign_run
-        return ga_assign_run(self.d, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
-                             gen_base=gen_base)
-
-
-class _MeetingIslands:
-    """Island engine of a MeetingScheduleDomain: ``ga_meeting_kernel`` / its twin (optimize/ga_meeting.py)."""
-
-    def __init__(self, tables: dict):
-        self.tables = tables
+    def __init__(self, names, init, run):
+        self.names, self.init, self.run = names, init, run
 
     def name(self, device) -> str:
-        return "ga_meeting_kernel" if device.type == "cuda" else "ga_meeting_twin"
-
-    def init(self, n: int, P: int, seed: int, island_base: int):
-        from .ga_meeting import ga_meeting_init, ga_meeting_price
-        pop = ga_meeting_init(self.tables, n, P, seed, island_base)
-        return pop, ga_meeting_price(self.tables, pop)
-
-    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
-        from .ga_meeting import ga_meeting_run
-        return ga_meeting_run(self.tables, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
-                              gen_base=gen_base)
-
-
-class _SubsetIslands:
-    """Island engine of a FeatureSubsetDomain with the built-in naive-Bayes evaluator:
-    ``ga_subset_kernel`` / its twin (optimize/ga_subset.py)."""
-
-    def __init__(self, tables: dict, device):
-        self.tables, self.device = tables, device
-
-    def name(self, device) -> str:
-        return "ga_subset_kernel" if device.type == "cuda" else "ga_subset_host"
-
-    def init(self, n: int, P: int, seed: int, island_base: int):
-        from .ga_subset import ga_subset_init, ga_subset_price, pack_masks
-        pop = ga_subset_init(self.tables, n, P, seed, island_base)
-        return pop, ga_subset_price(self.tables, pack_masks(pop), self.device)
-
-    def run(self, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device, gen_base=0):
-        from .ga_subset import ga_subset_run
-        return ga_subset_run(self.tables, pop, cost, G, m, r, purge_first, mutate, seed, island_base, device,
-                             gen_base=gen_base)
+        return self.names[0] if device.type == "cuda" else self.names[1]
 
 
 class GeneticAlgorithm:
@@ -550,22 +496,29 @@ class GeneticAlgorithm:
         d = self.d
         if self.use_kernel is False or getattr(d, "groups", None) or self.recovery is not None:
             return None
-        P, r, m = self.Pp, self.r, self.m
-        if not (2 <= P <= 64 and 1 <= r <= min(P, 32) and 1 <= m <= P and (self.purge_first or P + r <= 64)):
+        from functools import partial
+        from . import ga, ga_meeting as gm, ga_subset as gs
+        P, r = self.Pp, self.r
+        if not ga.ga_pool_ok(P, self.m, r, self.purge_first):
             return None
         if isinstance(d, AssignmentDomain):
-            lds = (2 * P + 2 * r) * d.L * 2 + (2 * P + 2 * r) * 8
-            return _AssignIslands(d) if lds <= 64 * 1024 and d.V <= 32767 else None
+            if ga.ga_assign_lds(P, d.L, r) > 64 * 1024 or d.V > 32767:
+                return None
+            return _Islands(("ga_assign_kernel", "ga_twin"), partial(ga.ga_assign_init, d), partial(ga.ga_assign_run, d))
         if self.use_kernel is True or d.device.type == "cuda":
-            from .ga_meeting import ga_meeting_lds, meeting_tables
-            tables = meeting_tables(d)      # None unless a MeetingScheduleDomain within the kernel's limits
-            if tables is not None and ga_meeting_lds(P, d.L, r) <= 64 * 1024:
-                return _MeetingIslands(tables)
-            from .ga_subset import ROW_CAP, ga_subset_lds, subset_tables
-            if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3 and d.loglik.shape[0] <= ROW_CAP:
-                tables = subset_tables(d)   # None unless a FeatureSubsetDomain with the built-in evaluator
-                if tables is not None and ga_subset_lds(tables["N"], tables["F"], tables["C"]) <= 48 * 1024:
-                    return _SubsetIslands(tables, d.device)
+            tb = gm.meeting_tables(d)       # None unless a MeetingScheduleDomain within the kernel's limits
+            if tb is not None and gm.ga_meeting_lds(P, d.L, r) <= 64 * 1024:
+                def init(n, P, seed, island_base):
+                    pop = gm.ga_meeting_init(tb, n, P, seed, island_base)
+                    return pop, gm.ga_meeting_price(tb, pop)
+                return _Islands(("ga_meeting_kernel", "ga_meeting_twin"), init, partial(gm.ga_meeting_run, tb))
+            if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3 and d.loglik.shape[0] <= gs.ROW_CAP:
+                tb = gs.subset_tables(d)    # None unless a FeatureSubsetDomain with the built-in evaluator
+                if tb is not None and gs.ga_subset_lds(tb["N"], tb["F"], tb["C"]) <= 48 * 1024:
+                    def init(n, P, seed, island_base):
+                        pop = gs.ga_subset_init(tb, n, P, seed, island_base)
+                        return pop, gs.ga_subset_price(tb, gs.pack_masks(pop), d.device)
+                    return _Islands(("ga_subset_kernel", "ga_subset_host"), init, partial(gs.ga_subset_run, tb))
         return None
 
     def _run_islands(self, comm, engine) -> OptResult:
