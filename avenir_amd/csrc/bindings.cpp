@@ -1472,18 +1472,18 @@ void ga_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict
                  (unsigned long long)gen_base, cur_stream(cost));
 }
 
-// island GA over a meeting-schedule domain (optim.hip::ga_meeting_kernel).  The domain tensors are
-// small; they are read back once here so that no index, mask bit or time can take the kernel out of
-// its LDS tables.
-void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,
-                const at::Tensor& share, const at::Tensor& member, const at::Tensor& role_w, const at::Tensor& blocked,
-                const at::Tensor& ordered, double invalid, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& hist,
-                int64_t G, int64_t m, int64_t r, bool purge_first, bool mutate, int64_t seed, int64_t island_base,
-                int64_t gen_base) {
+// The meeting-schedule domain of the K22 kernels (optim.hip::ga_meeting_kernel, sa_meeting_kernel).
+// The domain tensors are small; they are read back once here so that no index, mask bit or time can
+// take a kernel out of its LDS tables.
+static avk::GaMeetingDomain meeting_domain(const char* who, const at::Tensor& days, const at::Tensor& hours,
+                                           const at::Tensor& minutes, const at::Tensor& dur, const at::Tensor& share,
+                                           const at::Tensor& member, const at::Tensor& role_w,
+                                           const at::Tensor& blocked, const at::Tensor& ordered) {
   for (const at::Tensor* t : {&days, &hours, &minutes, &dur, &share, &member, &blocked, &ordered}) {
     CHECK_DEV((*t));
     CHECK_DTYPE((*t), at::kInt);
-    TORCH_CHECK(t->is_contiguous(), "ga_meeting: domain tensors must be contiguous");
+    TORCH_CHECK(t->is_contiguous(), who, ": domain tensors must be contiguous");
+    TORCH_CHECK(t->device() == days.device(), who, ": domain tensors on one device");
   }
   CHECK_DEV(role_w);
   CHECK_DTYPE(role_w, at::kFloat);
@@ -1494,14 +1494,12 @@ void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tenso
   TORCH_CHECK(ordered.dim() == 2 && ordered.size(1) == 2, "ordered must be [no, 2]");
   const int64_t nd = days.numel(), nh = hours.numel(), nm = minutes.numel(), M = dur.numel(), Q = member.numel();
   const int64_t nb = blocked.size(0), no = ordered.size(0);
-  TORCH_CHECK(M >= 1 && M <= 32, "ga_meeting: 1 <= M <= 32 meetings");
-  TORCH_CHECK(Q >= 1 && Q <= 256 && role_w.numel() == Q, "ga_meeting: 1 <= Q <= 256 people, role_w [Q]");
+  TORCH_CHECK(M >= 1 && M <= 32, who, ": 1 <= M <= 32 meetings");
+  TORCH_CHECK(Q >= 1 && Q <= 256 && role_w.numel() == Q, who, ": 1 <= Q <= 256 people, role_w [Q]");
+  TORCH_CHECK(role_w.device() == days.device(), who, ": domain tensors on one device");
   TORCH_CHECK(share.numel() == M, "share must be [M]");
   TORCH_CHECK(nd >= 1 && nd <= 32 && nh >= 1 && nh <= 32 && nm >= 1 && nm <= 32, "value tables of 1..32 entries");
   TORCH_CHECK(nb <= 16 && no <= 16, "at most 16 blocked entries and 16 ordered pairs");
-  const int64_t L = 3 * M;
-  const auto [I, P] = ga_check("ga_meeting", pop, L, pop_cost, hist, G, m, r, purge_first, gen_base);
-  TORCH_CHECK(avk::ga_meeting_lds((int)P, (int)L, (int)r) <= 64 * 1024, "ga_meeting: more than 64 KiB of LDS");
   // the domain on the host: mask bits < M, pairs < M, times that stay exact in int32 and fp32
   const uint32_t mmask = M == 32 ? 0xffffffffu : ((1u << M) - 1u);
   auto host = [](const at::Tensor& t) { return t.cpu(); };
@@ -1551,18 +1549,35 @@ void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tenso
     const int* e = ho.data_ptr<int>() + 2 * o;
     TORCH_CHECK(e[0] >= 0 && e[0] < M && e[1] >= 0 && e[1] < M, "ordered: meeting indices must be < M");
   }
-  if (pop.numel()) {
-    const at::Tensor hi = pop.view({-1, 3}).amax(0).cpu(), lo = pop.min().cpu();
-    const int16_t* h = hi.data_ptr<int16_t>();
-    TORCH_CHECK(lo.item<int16_t>() >= 0 && h[0] < nd && h[1] < nh && h[2] < nm,
-                "solution indices out of range of their value tables");
-  }
+  return avk::GaMeetingDomain{days.data_ptr<int>(), hours.data_ptr<int>(), minutes.data_ptr<int>(), (int)nd, (int)nh,
+                              (int)nm, dur.data_ptr<int>(), reinterpret_cast<const unsigned*>(share.data_ptr<int>()),
+                              (int)M, reinterpret_cast<const unsigned*>(member.data_ptr<int>()),
+                              role_w.data_ptr<float>(), (int)Q, blocked.data_ptr<int>(), (int)nb,
+                              ordered.data_ptr<int>(), (int)no};
+}
+
+// sol int16 [..., 3 M]: every (day, hour, minute) index inside its value table
+static void meeting_indices(const avk::GaMeetingDomain& dom, const at::Tensor& sol) {
+  if (!sol.numel()) return;
+  const at::Tensor hi = sol.view({-1, 3}).amax(0).cpu(), lo = sol.min().cpu();
+  const int16_t* h = hi.data_ptr<int16_t>();
+  TORCH_CHECK(lo.item<int16_t>() >= 0 && h[0] < dom.nd && h[1] < dom.nh && h[2] < dom.nm,
+              "solution indices out of range of their value tables");
+}
+
+void ga_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,
+                const at::Tensor& share, const at::Tensor& member, const at::Tensor& role_w, const at::Tensor& blocked,
+                const at::Tensor& ordered, double invalid, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& hist,
+                int64_t G, int64_t m, int64_t r, bool purge_first, bool mutate, int64_t seed, int64_t island_base,
+                int64_t gen_base) {
+  const avk::GaMeetingDomain dom =
+      meeting_domain("ga_meeting", days, hours, minutes, dur, share, member, role_w, blocked, ordered);
+  const int64_t L = 3 * dom.M;
+  const auto [I, P] = ga_check("ga_meeting", pop, L, pop_cost, hist, G, m, r, purge_first, gen_base);
+  TORCH_CHECK(avk::ga_meeting_lds((int)P, (int)L, (int)r) <= 64 * 1024, "ga_meeting: more than 64 KiB of LDS");
+  TORCH_CHECK(pop.device() == days.device(), "ga_meeting: tensors on one device");
+  meeting_indices(dom, pop);
   DevGuard g(pop.device());
-  avk::GaMeetingDomain dom{days.data_ptr<int>(), hours.data_ptr<int>(), minutes.data_ptr<int>(), (int)nd, (int)nh,
-                           (int)nm, dur.data_ptr<int>(), reinterpret_cast<const unsigned*>(share.data_ptr<int>()),
-                           (int)M, reinterpret_cast<const unsigned*>(member.data_ptr<int>()),
-                           role_w.data_ptr<float>(), (int)Q, blocked.data_ptr<int>(), (int)nb,
-                           ordered.data_ptr<int>(), (int)no};
   avk::ga_meeting(dom, (float)invalid, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(), hist.data_ptr<float>(),
                   (int)I, (int)P, (int)G, (int)m, (int)r, purge_first ? 1 : 0, mutate ? 1 : 0,
                   (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(pop));
@@ -1618,6 +1633,88 @@ void ga_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tens
                  (int)min_size, (int)max_size, (float)invalid, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(),
                  hist.data_ptr<float>(), (int)I, (int)P, (int)G, (int)m, (int)r, purge_first ? 1 : 0, mutate ? 1 : 0,
                  (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(LL));
+}
+
+// The checks shared by the SA chain bindings (optim.hip::sa_meeting_kernel, sa_subset_kernel): the
+// resumable state on one device and Philox counters that stay inside 64 bits.  Returns the chain
+// count and the run.
+static std::pair<int64_t, avk::SaRun> sa_check(const char* who, int64_t L, const at::Tensor& sol,
+                                               const at::Tensor& cur_cost, const at::Tensor& best_sol,
+                                               const at::Tensor& best_cost, const at::Tensor& stats, int64_t iters,
+                                               double t0, double cool, int64_t interval, bool geometric,
+                                               int64_t max_retry, int64_t seed, int64_t offset, int64_t it_begin,
+                                               double temp_start, int64_t chain_base) {
+  TORCH_CHECK(max_retry >= 0 && max_retry < (1LL << 20), who, ": 0 <= max_retry < 2^20");
+  TORCH_CHECK(iters >= 0 && it_begin >= 0 && iters < (1LL << 40) && it_begin < (1LL << 40) &&
+              it_begin + iters < (1LL << 40), who, ": 0 <= iters, it_begin and it_begin + iters < 2^40");
+  // (it_begin + iters) (max_retry + 1) < 2^60: the sum with offset must stay below 2^63
+  TORCH_CHECK(offset >= 0 && offset < (1LL << 62), who, ": 0 <= offset < 2^62 (Philox counters must not wrap)");
+  TORCH_CHECK(chain_base >= 0 && chain_base < (1LL << 62), who, ": 0 <= chain_base < 2^62");
+  for (const at::Tensor* t : {&sol, &best_sol}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kShort);
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == L && t->is_contiguous(), who, ": sol and best_sol must be contiguous [P, ",
+                L, "]");
+  }
+  const int64_t P = sol.size(0);
+  TORCH_CHECK(best_sol.size(0) == P && P < (1LL << 31), who, ": best_sol must have the shape of sol, P < 2^31");
+  for (const at::Tensor* t : {&cur_cost, &best_cost}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kFloat);
+    TORCH_CHECK(t->is_contiguous() && t->dim() == 1 && t->numel() == P, who, ": cost vectors must be [P]");
+  }
+  CHECK_DEV(stats);
+  CHECK_DTYPE(stats, at::kLong);
+  TORCH_CHECK(stats.is_contiguous() && stats.numel() >= 4, who, ": stats needs 4 entries (3 counters + temperature)");
+  for (const at::Tensor* t : {&cur_cost, &best_sol, &best_cost, &stats})
+    TORCH_CHECK(t->device() == sol.device(), who, ": tensors on one device");
+  return {P, avk::SaRun{(long long)iters, (long long)it_begin, (float)t0, (float)cool, (long long)interval,
+                        geometric ? 1 : 0, (int)max_retry, (unsigned long long)seed, (unsigned long long)offset,
+                        (float)temp_start, (long long)chain_base}};
+}
+
+void sa_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,
+                const at::Tensor& share, const at::Tensor& member, const at::Tensor& role_w, const at::Tensor& blocked,
+                const at::Tensor& ordered, at::Tensor& sol, at::Tensor& cur_cost, at::Tensor& best_sol,
+                at::Tensor& best_cost, int64_t iters, double t0, double cool, int64_t interval, bool geometric,
+                int64_t max_retry, int64_t seed, int64_t offset, at::Tensor& stats, int64_t it_begin, double temp_start,
+                int64_t chain_base) {
+  const avk::GaMeetingDomain dom =
+      meeting_domain("sa_meeting", days, hours, minutes, dur, share, member, role_w, blocked, ordered);
+  const auto [P, run] = sa_check("sa_meeting", 3 * (int64_t)dom.M, sol, cur_cost, best_sol, best_cost, stats, iters, t0,
+                                 cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, chain_base);
+  TORCH_CHECK(sol.device() == days.device(), "sa_meeting: tensors on one device");
+  meeting_indices(dom, sol);
+  meeting_indices(dom, best_sol);
+  DevGuard g(sol.device());
+  avk::sa_meeting(dom, sol.data_ptr<int16_t>(), cur_cost.data_ptr<float>(), best_sol.data_ptr<int16_t>(),
+                  best_cost.data_ptr<float>(), (int)P, run,
+                  reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), cur_stream(sol));
+}
+
+// waves_per_chain: 0 lets the launcher choose; 1, 2, 4, 8 or 16 forces it (no result depends on it)
+void sa_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tensor& labels, int64_t min_size,
+               int64_t max_size, at::Tensor& sol, at::Tensor& cur_cost, at::Tensor& best_sol, at::Tensor& best_cost,
+               int64_t iters, double t0, double cool, int64_t interval, bool geometric, int64_t max_retry,
+               int64_t seed, int64_t offset, at::Tensor& stats, int64_t it_begin, double temp_start,
+               int64_t chain_base, int64_t waves_per_chain) {
+  subset_check(LL, log_prior, labels, "sa_subset");
+  const int64_t N = LL.size(0), F = LL.size(1), C = LL.size(2);
+  TORCH_CHECK(min_size >= 0 && min_size <= max_size && max_size <= 32, "sa_subset: 0 <= min_size <= max_size <= 32");
+  TORCH_CHECK(waves_per_chain == 0 || waves_per_chain == 1 || waves_per_chain == 2 || waves_per_chain == 4 ||
+              waves_per_chain == 8 || waves_per_chain == 16, "sa_subset: waves_per_chain must be 0, 1, 2, 4, 8 or 16");
+  const auto [P, run] = sa_check("sa_subset", F, sol, cur_cost, best_sol, best_cost, stats, iters, t0, cool, interval,
+                                 geometric, max_retry, seed, offset, it_begin, temp_start, chain_base);
+  TORCH_CHECK(sol.device() == LL.device(), "sa_subset: tensors on one device");
+  for (const at::Tensor* t : {&sol, &best_sol})
+    if (t->numel())
+      TORCH_CHECK(t->min().item<int>() >= 0 && t->max().item<int>() <= 1, "sa_subset: masks must be 0 or 1");
+  DevGuard g(LL.device());
+  avk::sa_subset(LL.data_ptr<float>(), log_prior.data_ptr<float>(), labels.data_ptr<int>(), (int)N, (int)F, (int)C,
+                 (int)min_size, (int)max_size, sol.data_ptr<int16_t>(), cur_cost.data_ptr<float>(),
+                 best_sol.data_ptr<int16_t>(), best_cost.data_ptr<float>(), (int)P, run,
+                 reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), (int)waves_per_chain,
+                 cur_stream(LL));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4447,7 +4544,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("ga_meeting_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_meeting_lds((int)P, (int)L, (int)r); });
   m.def("subset_errors", &subset_errors);
   m.def("ga_subset", &ga_subset);
-  m.def("ga_subset_lds", [](int64_t N, int64_t F, int64_t C) { return (int64_t)avk::ga_subset_lds((int)N, (int)F, (int)C); });
+  m.def("sa_meeting", &sa_meeting);
+  m.def("sa_meeting_lds", [](int64_t M) { return (int64_t)avk::sa_meeting_lds((int)M); });
+  m.def("sa_subset", &sa_subset);
+  m.def("sa_subset_plan", [](int64_t N, int64_t F, int64_t C, int64_t P, int64_t w) {
+    const avk::SaSubsetPlan pl = avk::sa_subset_plan((int)N, (int)F, (int)C, (int)P, (int)w);
+    return std::make_tuple((int64_t)pl.threads, (int64_t)pl.waves, (int64_t)pl.rows, (int64_t)pl.grid, (int64_t)pl.lds);
+  });
+  m.def("ga_subset_lds",[](int64_t N, int64_t F, int64_t C) { return (int64_t)avk::ga_subset_lds((int)N, (int)F, (int)C); });
   m.def("smote_lines", &smote_lines);
   m.def("format_device", &format_device);
   m.def("pairs_within", &pairs_within);

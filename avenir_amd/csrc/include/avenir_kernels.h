@@ -158,6 +158,31 @@ void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swa
                int geometric, int max_retry, unsigned long long seed, unsigned long long offset,
                int it_begin, float temp_start, unsigned long long* stats, long long chain_base,
                hipStream_t stream);
+// SA chains over the meeting-schedule and feature-subset domains (one launch, resumable like
+// sa_assign): sol / best_sol int16 [P][L], cur_cost / best_cost [P] in and out, stats[4] = better,
+// worse_accepted, rejected (added) and the hand-off temperature's bits.  Row p is global chain
+// chain_base + p; moves [it_begin, it_begin + iters) with 64-bit Philox counters throughout.
+struct SaRun {
+  long long iters, it_begin;
+  float t0, cool;
+  long long interval;
+  int geometric, max_retry;
+  unsigned long long seed, offset;
+  float temp_start;
+  long long chain_base;
+};
+size_t sa_meeting_lds(int M);
+void sa_meeting(const GaMeetingDomain& dom, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P,
+                const SaRun& run, unsigned long long* stats, hipStream_t stream);
+struct SaSubsetPlan {
+  int threads, waves, rows, grid;  // workgroup size, waves per chain, rows per tile, workgroups
+  size_t lds;                      // bytes of dynamic LDS: the row tile and its labels
+};
+// waves_per_chain: 1, 2, 4, 8 or 16 (8 and 16 take 1,024 threads), or 0 for the launcher's choice
+SaSubsetPlan sa_subset_plan(int N, int F, int C, int P, int waves_per_chain);
+void sa_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P, const SaRun& run,
+               unsigned long long* stats, int waves_per_chain, hipStream_t stream);
 
 // ---- linear.hip (K13) ----------------------------------------------------------------------
 int glm_grid(long long n);

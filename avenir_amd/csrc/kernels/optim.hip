@@ -400,22 +400,25 @@ struct MtLds {  // the staged domain
   int M, Q, nb, no;
 };
 
-// start second and day bit of meeting i of solution c
+// start second and day bit of meeting i of solution c.  S is the element stride of c, st and db:
+// 1 for rows, 64 for the lane-private [j][64] columns of the annealing kernel.
+template <int S = 1>
 __device__ __forceinline__ void mt_place(const MtLds& D, const short* c, int i, int* st, unsigned* db) {
-  const int d = c[3 * i];
-  st[i] = (D.days[d] - 1) * 86400 + D.hours[c[3 * i + 1]] * 3600 + D.minutes[c[3 * i + 2]] * 60;
-  db[i] = 1u << d;
+  const int d = c[3 * i * S];
+  st[i * S] = (D.days[d] - 1) * 86400 + D.hours[c[(3 * i + 1) * S]] * 3600 + D.minutes[c[(3 * i + 2) * S]] * 60;
+  db[i * S] = 1u << d;
 }
 
+template <int S = 1>
 __device__ __forceinline__ bool mt_valid(const MtLds& D, const int* st) {
   bool ok = true;
   for (int i = 1; i < D.M; ++i) {
     unsigned mk = D.share[i] & ((1u << i) - 1u);  // share is symmetric: pairs j < i
-    const int si = st[i], ei = si + D.dur[i];
+    const int si = st[i * S], ei = si + D.dur[i];
     while (mk) {
       const int j = __ffs(mk) - 1;
       mk &= mk - 1;
-      const int sj = st[j];
+      const int sj = st[j * S];
       ok &= !(si < sj + D.dur[j] && sj < ei);
     }
   }
@@ -425,17 +428,18 @@ __device__ __forceinline__ bool mt_valid(const MtLds& D, const int* st) {
     while (mk) {
       const int i = __ffs(mk) - 1;
       mk &= mk - 1;
-      const int si = st[i];
+      const int si = st[i * S];
       ok &= !(si < be && bs < si + D.dur[i]);
     }
   }
   for (int o = 0; o < D.no; ++o) {
     const int a = D.ordered[2 * o], b = D.ordered[2 * o + 1];
-    ok &= st[a] + D.dur[a] <= st[b];
+    ok &= st[a * S] + D.dur[a] <= st[b * S];
   }
   return ok;
 }
 
+template <int S = 1>
 __device__ __forceinline__ float mt_cost(const MtLds& D, const unsigned* db) {
 #pragma clang fp contract(off)  // the twin rounds pc * w and the add separately
   float num = 0.f, den = 0.f;
@@ -448,7 +452,7 @@ __device__ __forceinline__ float mt_cost(const MtLds& D, const unsigned* db) {
     while (mk) {
       const int i = __ffs(mk) - 1;
       mk &= mk - 1;
-      dm |= db[i];
+      dm |= db[i * S];
       booked += D.dur[i];
     }
     const int nday = __popc(dm);
@@ -462,16 +466,9 @@ __device__ __forceinline__ float mt_cost(const MtLds& D, const unsigned* db) {
   return num / fmaxf(den, 1e-12f);
 }
 
-__global__ __launch_bounds__(64) void ga_meeting_kernel(
-    avk::GaMeetingDomain dom, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
-    float* __restrict__ hist, GaArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char gm_lds[];
-  const int M = dom.M, L = 3 * M, Ms = M | 1;  // Ms: odd stride of the lane-private rows
-  GaPool<short> W;
-  unsigned char* cur = W.carve(gm_lds, A.P, L, A.r);
-  int* st_all = reinterpret_cast<int*>(cur);  cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));   // [2r][Ms] starts
-  unsigned* db_all = reinterpret_cast<unsigned*>(cur); cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));  // day bits
-  int* di = reinterpret_cast<int*>(cur);      // the domain, MT_DOM_INTS dwords
+// The domain -> MT_DOM_INTS dwords of LDS at di, by the 64 lanes of a wave (every table and list has
+// at most 64 entries but member / role_w); the caller's barrier follows.
+__device__ __forceinline__ MtLds mt_stage(const avk::GaMeetingDomain& dom, int* di, int lane) {
   int* l_days = di;
   int* l_hours = l_days + MT_MAX_CARD;
   int* l_minutes = l_hours + MT_MAX_CARD;
@@ -481,13 +478,10 @@ __global__ __launch_bounds__(64) void ga_meeting_kernel(
   float* l_role = reinterpret_cast<float*>(l_member + MT_MAX_Q);
   int* l_blocked = reinterpret_cast<int*>(l_role + MT_MAX_Q);
   int* l_ordered = l_blocked + 3 * MT_MAX_LIST;
-
-  const int lane = threadIdx.x;
-  const unsigned long long gi = (unsigned long long)(A.island_base + (long long)blockIdx.x);
   if (lane < dom.nd) l_days[lane] = dom.days[lane];
   if (lane < dom.nh) l_hours[lane] = dom.hours[lane];
   if (lane < dom.nm) l_minutes[lane] = dom.minutes[lane];
-  if (lane < M) {
+  if (lane < dom.M) {
     l_dur[lane] = dom.dur[lane];
     l_share[lane] = dom.share[lane];
   }
@@ -497,8 +491,22 @@ __global__ __launch_bounds__(64) void ga_meeting_kernel(
   }
   if (lane < 3 * dom.nb) l_blocked[lane] = dom.blocked[lane];
   if (lane < 2 * dom.no) l_ordered[lane] = dom.ordered[lane];
-  const MtLds D{l_days, l_hours, l_minutes, l_dur, l_blocked, l_ordered, l_share, l_member, l_role,
-                M, dom.Q, dom.nb, dom.no};
+  return MtLds{l_days, l_hours, l_minutes, l_dur, l_blocked, l_ordered, l_share, l_member, l_role,
+               dom.M, dom.Q, dom.nb, dom.no};
+}
+
+__global__ __launch_bounds__(64) void ga_meeting_kernel(
+    avk::GaMeetingDomain dom, float invalid, short* __restrict__ pop, float* __restrict__ pop_cost,
+    float* __restrict__ hist, GaArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gm_lds[];
+  const int M = dom.M, L = 3 * M, Ms = M | 1;  // Ms: odd stride of the lane-private rows
+  GaPool<short> W;
+  unsigned char* cur = W.carve(gm_lds, A.P, L, A.r);
+  int* st_all = reinterpret_cast<int*>(cur);  cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));   // [2r][Ms] starts
+  unsigned* db_all = reinterpret_cast<unsigned*>(cur); cur += ga_a16((size_t)2 * A.r * Ms * sizeof(int));  // day bits
+  const int lane = threadIdx.x;
+  const unsigned long long gi = (unsigned long long)(A.island_base + (long long)blockIdx.x);
+  const MtLds D = mt_stage(dom, reinterpret_cast<int*>(cur), lane);  // the frame's first barrier covers it
   ga_island(W, A, L, pop, pop_cost, hist, lane, 64, [&](unsigned long long ctr0) {
     if (lane < 2 * A.r) {
       const int h = lane & 1;
@@ -784,6 +792,281 @@ __global__ __launch_bounds__(1024) void ga_subset_kernel(
   });
 }
 
+// ---- simulated-annealing chains over the meeting-schedule and feature-subset domains ------------
+// Reference: the Spark simulatedAnnealing job and SimulatedAnnealingOptimizer
+// (P/mlextra/optsolo.py:34-88, which `fesel sa` drives).  Chain g = chain_base + p is GLOBAL; move
+// `it` of [it_begin, it_begin + iters):
+//   1. attempts tr = 0..max_retry draw Philox(seed, offset + it (max_retry + 1) + tr, g): word x
+//      picks the position, word y the value; the first attempt that gives a valid candidate is the
+//      move, and without one nothing happens (no counter changes);
+//   2. the candidate is priced from scratch, so cur_cost is always the price of sol;
+//   3. cc <= c is accepted (`better`, also from c = inf); otherwise
+//      u(Philox(seed ^ 0x9E3779B97F4A7C15, offset + it, g).x) < sa_exp(-((cc - c) / max(temp, 1e-12)))
+//      is accepted (`worse_accepted`); the rest is `rejected`;
+//   4. on acceptance sol = cand, c = cc, and c < best_cost replaces the best;
+//   5. cooling after every move, when interval > 0 and (it + 1) % interval == 0: temp * cool, or
+//      max(t0 - (float)(it + 1) cool, 1e-12), product and difference rounded separately.
+// Every fp32 operation is rounded on its own (no contraction) and sa_exp is built from such
+// operations alone, so optimize/sa.py::sa_chains_reference equals the kernels bit for bit, the
+// Metropolis decision included.  What a solution is, when it is valid and what it costs is the
+// domain's: each kernel supplies propose / price / settle / improved to sa_chain.
+struct SaArgs {
+  int P;
+  long long iters, it_begin;
+  float t0, cool;
+  long long interval;
+  int geometric, max_retry;
+  unsigned long long seed, offset;
+  float temp_start;
+  long long chain_base;
+};
+
+// exp(x) for x <= 0 (clamped to -87, where the result is still a normal number): k = rint(x log2 e),
+// two-constant Cody-Waite reduction, degree-6 Taylor polynomial by Horner, exact scaling by 2^k.
+// Within 1e-6 relative of exp; optimize/sa.py::sa_exp is the same operations in the same order.
+__device__ __forceinline__ float sa_exp(float x) {
+#pragma clang fp contract(off)
+  x = fmaxf(x, -87.f);
+  const float k = rintf(x * 1.4426950408889634f);
+  float r = x - k * 0.693359375f;  // 355 / 512: the product is exact
+  r = r - k * -2.12194440e-4f;
+  float p = 1.f / 720.f;
+  p = p * r + 1.f / 120.f;
+  p = p * r + 1.f / 24.f;
+  p = p * r + 1.f / 6.f;
+  p = p * r + 0.5f;
+  p = p * r + 1.f;
+  p = p * r + 1.f;
+  return ldexpf(p, (int)k);
+}
+
+// step 3: 0 rejected, 1 better, 2 worse but accepted
+__device__ __forceinline__ int sa_accept(const SaArgs& A, long long it, unsigned long long gp, float cc, float c,
+                                         float temp) {
+#pragma clang fp contract(off)
+  if (cc <= c) return 1;
+  const av::u4 r = av::philox_draw(A.seed ^ 0x9e3779b97f4a7c15ull, A.offset + (unsigned long long)it, gp);
+  const float q = (cc - c) / fmaxf(temp, 1e-12f);
+  return av::u32_to_unit(r.x) < sa_exp(-q) ? 2 : 0;
+}
+
+// step 5
+__device__ __forceinline__ float sa_cool(const SaArgs& A, long long it, float temp) {
+#pragma clang fp contract(off)
+  if (A.interval > 0 && (it + 1) % A.interval == 0) {
+    if (A.geometric) return temp * A.cool;
+    const float d = (float)(it + 1) * A.cool;
+    return fmaxf(A.t0 - d, 1e-12f);
+  }
+  return temp;
+}
+
+struct SaChain {  // what a chain carries besides its solution
+  float c, bc, temp;
+  unsigned long long better, worse, rejected;
+};
+
+// The moves of one chain.  propose(x, y) -> bool: one attempt; it leaves a valid candidate pending
+// and takes an invalid one back.  price(moved) -> float: the pending candidate's cost; every thread
+// calls it every move (it may hold barriers), its value counts only where moved.  settle(accepted):
+// the candidate becomes the solution, or is taken back.  improved(): the solution is the new best.
+// A chain that is not `live` proposes nothing and only keeps price's barriers.
+template <class Propose, class Price, class Settle, class Improved>
+__device__ __forceinline__ void sa_chain(const SaArgs& A, unsigned long long gp, bool live, SaChain& S,
+                                         Propose propose, Price price, Settle settle, Improved improved) {
+  const unsigned long long R = (unsigned long long)A.max_retry + 1ull;
+  for (long long it = A.it_begin; it < A.it_begin + A.iters; ++it) {
+    bool moved = false;
+    if (live)
+      for (int tr = 0; tr <= A.max_retry && !moved; ++tr) {
+        const av::u4 q = av::philox_draw(A.seed, A.offset + (unsigned long long)it * R + (unsigned long long)tr, gp);
+        moved = propose(q.x, q.y);
+      }
+    const float cc = price(moved);
+    if (moved) {
+      const int a = sa_accept(A, it, gp, cc, S.c, S.temp);
+      settle(a != 0);
+      if (a) {
+        S.c = cc;
+        if (a == 1) ++S.better; else ++S.worse;
+        if (S.c < S.bc) {
+          S.bc = S.c;
+          improved();
+        }
+      } else {
+        ++S.rejected;
+      }
+    }
+    S.temp = sa_cool(A, it, S.temp);
+  }
+}
+
+// stats[0..2] += the chain's counters; local chain 0 leaves the hand-off temperature's bits in stats[3]
+__device__ __forceinline__ void sa_report(unsigned long long* __restrict__ stats, long long p, const SaChain& S) {
+  if (!stats) return;
+  if (p == 0) stats[3] = (unsigned long long)__float_as_uint(S.temp);
+  if (S.better) atomicAdd(&stats[0], S.better);
+  if (S.worse) atomicAdd(&stats[1], S.worse);
+  if (S.rejected) atomicAdd(&stats[2], S.rejected);
+}
+
+// Meeting schedules: one chain per lane, 64-lane workgroups.  The chain's index triples, start
+// seconds and day bits are columns `lane` of [3 M][64] short, [M][64] int and [M][64] unsigned LDS
+// tiles (lane-private, one bank per lane), the domain is staged behind them.  A move is the island
+// kernel's mutation: one index to a different value of its table (a table of one value leaves the
+// solution as it is); it touches one meeting, so mt_place runs for that meeting alone, and taking a
+// move back places the old value again.  The best solution goes to global memory on improvement.
+__global__ __launch_bounds__(64) void sa_meeting_kernel(
+    avk::GaMeetingDomain dom, short* __restrict__ sol, float* __restrict__ cur_cost, short* __restrict__ best_sol,
+    float* __restrict__ best_cost, unsigned long long* __restrict__ stats, SaArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sm_lds[];
+  const int M = dom.M, L = 3 * M;
+  const int lane = threadIdx.x;
+  short* s = reinterpret_cast<short*>(sm_lds) + lane;                                     // element j at s[j * 64]
+  int* st = reinterpret_cast<int*>(sm_lds + (size_t)L * 64 * sizeof(short)) + lane;       // start of meeting i at st[i * 64]
+  unsigned* db = reinterpret_cast<unsigned*>(st - lane + (size_t)M * 64) + lane;          // its day bit
+  const MtLds D = mt_stage(dom, reinterpret_cast<int*>(db - lane + (size_t)M * 64), lane);
+  const long long p = (long long)blockIdx.x * 64 + lane;
+  const bool live = p < A.P;
+  if (live)
+    for (int j = 0; j < L; ++j) s[j * 64] = sol[p * L + j];
+  __syncthreads();
+  if (!live) return;
+  for (int i = 0; i < M; ++i) mt_place<64>(D, s, i, st, db);
+  const unsigned long long gp = (unsigned long long)(A.chain_base + p);
+  short* bs = best_sol + p * L;
+  SaChain S{cur_cost[p], best_cost[p], A.temp_start, 0, 0, 0};
+  int pos = 0, mi = 0, card = 0, old = 0;
+  auto put = [&](int v) {
+    if (card > 1) {
+      s[pos * 64] = (short)v;
+      mt_place<64>(D, s, mi, st, db);
+    }
+  };
+  sa_chain(
+      A, gp, true, S,
+      [&](unsigned qp, unsigned qv) {
+        pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+        mi = pos / 3;
+        const int comp = pos - 3 * mi;
+        card = comp == 0 ? dom.nd : comp == 1 ? dom.nh : dom.nm;
+        old = s[pos * 64];
+        int v = min((int)(av::u32_to_unit(qv) * (float)(card - 1)), card - 2);
+        v += v >= old;
+        put(v);
+        const bool ok = mt_valid<64>(D, st);
+        if (!ok) put(old);
+        return ok;
+      },
+      [&](bool moved) { return moved ? mt_cost<64>(D, db) : 0.f; },
+      [&](bool accepted) {
+        if (!accepted) put(old);
+      },
+      [&] {
+        for (int j = 0; j < L; ++j) bs[j] = s[j * 64];
+      });
+  for (int j = 0; j < L; ++j) sol[p * L + j] = s[j * 64];
+  cur_cost[p] = S.c;
+  best_cost[p] = S.bc;
+  sa_report(stats, p, S);
+}
+
+// Feature subsets: a workgroup of 256 or 1,024 threads whose waves are split into chains of w waves
+// each (w = 1, 2, 4, 8 or 16).  All chains of the workgroup share the staged row tile (odd stride,
+// the labels behind it; a single tile stays resident for the whole launch).  Every lane of a chain
+// draws the same Philox words, so the chain's masks, costs and counters are wave-uniform and each
+// of its waves carries them; the candidate mask is handed to the scoring as a scalar.  A chain's
+// waves walk the tile's 64-row groups (wave `sub` takes groups sub, sub + w, ...), count misses by
+// ballot into a register, and the w partial counts meet in an integer LDS counter.  The counters
+// are three deep: move k adds to counter k % 3 and clears counter (k + 1) % 3, whose last readers
+// passed a barrier before, so one barrier per tile and move is enough.  Error counts are
+// integers: no result depends on w, the thread count or the tile size.
+constexpr int SA_FS_MAX_CHAINS = 16;  // chains per workgroup: 1,024 threads of one-wave chains
+
+__global__ __launch_bounds__(1024) void sa_subset_kernel(
+    const float* __restrict__ LL, const float* __restrict__ log_prior, const int* __restrict__ labels, int N, int F,
+    int C, int min_size, int max_size, short* __restrict__ sol, float* __restrict__ cur_cost,
+    short* __restrict__ best_sol, float* __restrict__ best_cost, unsigned long long* __restrict__ stats, SaArgs A,
+    int TR, int w) {
+  extern __shared__ __attribute__((aligned(16))) float fs_tile[];
+  __shared__ float s_prior[FS_MAX_C];
+  __shared__ int s_cnt[3][SA_FS_MAX_CHAINS];
+  const int tid = threadIdx.x, nt = blockDim.x, FC = F * C, stride = FC | 1;
+  const unsigned magic = 0xFFFFFFFFu / (unsigned)FC + 1u;
+  const int ntiles = (N + TR - 1) / TR;
+  int* s_lab = reinterpret_cast<int*>(fs_tile + (size_t)TR * stride);  // [TR] labels of the staged rows
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wsh = __ffs(w) - 1, ci = wave >> wsh, sub = wave & (w - 1), cpw = (nt >> 6) >> wsh;
+  const long long p = (long long)blockIdx.x * cpw + ci;
+  const bool live = p < A.P;
+  const unsigned long long gp = (unsigned long long)(A.chain_base + p);
+  if (tid < C) s_prior[tid] = log_prior[tid];
+  if (tid < 3 * SA_FS_MAX_CHAINS) (&s_cnt[0][0])[tid] = 0;
+  unsigned mk = 0, bmk = 0, cand = 0;
+  SaChain S{0.f, 0.f, A.temp_start, 0, 0, 0};
+  if (live) {
+    const bool in = lane < F;
+    mk = (unsigned)__ballot(in && sol[p * F + (in ? lane : 0)] != 0);
+    bmk = (unsigned)__ballot(in && best_sol[p * F + (in ? lane : 0)] != 0);
+    S.c = cur_cost[p];
+    S.bc = best_cost[p];
+  }
+  __syncthreads();
+  bool staged = false;
+  int k = 0;  // move of this launch
+  sa_chain(
+      A, gp, live, S,
+      [&](unsigned qp, unsigned) {
+        const int pos = min((int)(av::u32_to_unit(qp) * (float)F), F - 1);
+        cand = (unsigned)__builtin_amdgcn_readfirstlane((int)(mk ^ (1u << pos)));
+        const int sz = __popc(cand);
+        return sz >= min_size && sz <= max_size;
+      },
+      [&](bool moved) {
+        int* cnt = s_cnt[k % 3];
+        if (tid < SA_FS_MAX_CHAINS) s_cnt[(k + 1) % 3][tid] = 0;
+        ++k;
+        int n = 0;
+        for (int t = 0; t < ntiles; ++t) {
+          const long long n0 = (long long)t * TR;
+          const int nr = min(TR, N - (int)n0);
+          if (ntiles > 1 || !staged) {
+            fs_stage(fs_tile, LL, n0, nr, FC, stride, magic, tid, nt);
+            for (int e = tid; e < nr; e += nt) s_lab[e] = labels[n0 + e];
+            staged = true;
+            __syncthreads();
+          }
+          if (moved) {
+            const int ng = (nr + 63) >> 6;
+            for (int g = sub; g < ng; g += w) {
+              const int row = g * 64 + lane;
+              const int rr = min(row, nr - 1);  // lanes past the tile score its last row, uncounted
+              const bool miss = fs_row_miss_uniform(fs_tile + rr * stride, s_prior, C, cand, s_lab[rr]);
+              n += __popcll(__ballot(miss && row < nr));
+            }
+            if (t == ntiles - 1 && lane == 0 && n) atomicAdd(&cnt[ci], n);
+          }
+          __syncthreads();  // the counts are in; the tile may be staged again
+        }
+        return (float)__builtin_amdgcn_readfirstlane(cnt[ci]) / (float)N;
+      },
+      [&](bool accepted) {
+        if (accepted) mk = cand;
+      },
+      [&] { bmk = mk; });
+  if (live && sub == 0) {
+    if (lane < F) {
+      sol[p * F + lane] = (short)((mk >> lane) & 1u);
+      best_sol[p * F + lane] = (short)((bmk >> lane) & 1u);
+    }
+    if (lane == 0) {
+      cur_cost[p] = S.c;
+      best_cost[p] = S.bc;
+      sa_report(stats, p, S);
+    }
+  }
+}
+
 }  // namespace
 
 namespace avk {
@@ -887,6 +1170,64 @@ void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swa
   sa_assign_kernel<<<(P + 63) / 64, 64, lds, stream>>>(cost, L, V, conflict, swap, sol, cur_cost, best_sol,
                                                        best_cost, P, iters, t0, cool, interval, geometric, max_retry,
                                                        seed, offset, it_begin, temp_start, stats, chain_base);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+static SaArgs sa_args(const char* who, const SaRun& r, int P) {
+  if (r.iters < 0 || r.it_begin < 0 || r.max_retry < 0 || r.max_retry >= (1 << 20) ||
+      r.it_begin + r.iters >= (1LL << 40))
+    throw std::invalid_argument(std::string(who) + ": 0 <= max_retry < 2^20, 0 <= it_begin, iters, it_begin + iters < 2^40");
+  return SaArgs{P, r.iters, r.it_begin, r.t0, r.cool, r.interval, r.geometric, r.max_retry, r.seed, r.offset,
+                r.temp_start, r.chain_base};
+}
+
+size_t sa_meeting_lds(int M) {
+  return (size_t)3 * M * 64 * sizeof(short) + (size_t)2 * M * 64 * sizeof(int) + (size_t)MT_DOM_INTS * sizeof(int);
+}
+
+void sa_meeting(const GaMeetingDomain& dom, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P,
+                const SaRun& run, unsigned long long* stats, hipStream_t stream) {
+  if (dom.M < 1 || dom.M > MT_MAX_M || dom.Q < 1 || dom.Q > MT_MAX_Q)
+    throw std::invalid_argument("sa_meeting: 1 <= M <= 32, 1 <= Q <= 256");
+  if (dom.nd < 1 || dom.nd > MT_MAX_CARD || dom.nh < 1 || dom.nh > MT_MAX_CARD || dom.nm < 1 || dom.nm > MT_MAX_CARD)
+    throw std::invalid_argument("sa_meeting: value tables of 1..32 entries");
+  if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
+    throw std::invalid_argument("sa_meeting: at most 16 blocked entries and 16 ordered pairs");
+  const SaArgs A = sa_args("sa_meeting", run, P);
+  const size_t lds = sa_meeting_lds(dom.M);
+  if (lds > 64 * 1024) throw std::invalid_argument("sa_meeting: the chains' tiles exceed 64 KiB of LDS");
+  if (P <= 0 || run.iters <= 0) return;
+  sa_meeting_kernel<<<(P + 63) / 64, 64, lds, stream>>>(dom, sol, cur_cost, best_sol, best_cost, stats, A);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+// Workgroup size, waves per chain and tile rows of sa_subset.  Auto (waves_per_chain = 0): every
+// chain starts with all waves of its workgroup and w halves until at most 512 workgroups remain,
+// so few chains get many waves each and many chains share their tiles.
+SaSubsetPlan sa_subset_plan(int N, int F, int C, int P, int waves_per_chain) {
+  int nt = ga_subset_threads(N), w = waves_per_chain;
+  if (w == 0) {
+    w = nt / 64;
+    while (w > 1 && (long long)P * w / (nt / 64) > 512) w >>= 1;
+  } else {
+    if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
+      throw std::invalid_argument("sa_subset: waves_per_chain must be 0 (auto), 1, 2, 4, 8 or 16");
+    if (w > nt / 64) nt = 1024;
+  }
+  const int FC = F * C, TR = fs_tile_rows(FC, nt), cpw = nt / 64 / w;
+  return SaSubsetPlan{nt, w, TR, (P + cpw - 1) / cpw, (size_t)TR * (FC | 1) * sizeof(float) + (size_t)TR * sizeof(int)};
+}
+
+void sa_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P, const SaRun& run,
+               unsigned long long* stats, int waves_per_chain, hipStream_t stream) {
+  fs_check(N, F, C, "sa_subset");
+  const SaArgs A = sa_args("sa_subset", run, P);
+  const SaSubsetPlan pl = sa_subset_plan(N, F, C, std::max(P, 1), waves_per_chain);
+  if (pl.lds > 56 * 1024) throw std::invalid_argument("sa_subset: the row tile exceeds its LDS");
+  if (P <= 0 || run.iters <= 0) return;
+  sa_subset_kernel<<<pl.grid, pl.threads, pl.lds, stream>>>(LL, log_prior, labels, N, F, C, min_size, max_size, sol,
+                                                           cur_cost, best_sol, best_cost, stats, A, pl.rows, pl.waves);
   AV_HIP_CHECK(hipGetLastError());
 }
 

@@ -162,26 +162,28 @@ def ga_meeting_init(tables: dict, n_islands: int, P: int, seed: int, island_base
                           max_try)
 
 
+def _mutated(tables: dict, c: np.ndarray, qp: np.ndarray, qv: np.ndarray) -> np.ndarray:
+    """The kernels' move on copies of c [..., 3 M]: position from word qp, a different value of its
+    table from word qv; a one-value table keeps its value."""
+    cards = tables["cards"]
+    pos = _unit_index(u32_to_unit(qp), tables["L"])
+    old = np.take_along_axis(c, pos[..., None], axis=-1)[..., 0]
+    card = cards[pos]
+    v = np.minimum((u32_to_unit(qv) * np.maximum(card - 1, 1).astype(np.float32)).astype(np.int64),
+                   np.maximum(card - 2, 0))
+    cand = c.copy()
+    _set(cand, pos, np.where(card > 1, v + (v >= old), old))
+    return cand
+
+
 def ga_meeting_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
                          purge_first: bool, mutate: bool, seed: int, island_base: int,
                          gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Host twin of ``ga_meeting_kernel`` (all islands at once).  Returns (pop int16, cost float32,
     hist float32)."""
-    L, cards = tables["L"], tables["cards"]
-
-    def mutated(c, qp, qv):
-        pos = _unit_index(u32_to_unit(qp), L)
-        old = np.take_along_axis(c, pos[..., None], axis=-1)[..., 0]
-        card = cards[pos]
-        v = np.minimum((u32_to_unit(qv) * np.maximum(card - 1, 1).astype(np.float32)).astype(np.int64),
-                       np.maximum(card - 2, 0))
-        cand = c.copy()
-        _set(cand, pos, np.where(card > 1, v + (v >= old), old))         # a one-value table keeps its value
-        return cand
-
     # the cut falls between two meetings
     dom = GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16),
-                   ncut=tables["M"], scale=3, crossover=splice, mutated=mutated,
+                   ncut=tables["M"], scale=3, crossover=splice, mutated=lambda c, qp, qv: _mutated(tables, c, qp, qv),
                    valid=lambda c: ga_meeting_valid(tables, c), price=lambda kids: ga_meeting_price(tables, kids))
     return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
 
@@ -212,3 +214,51 @@ def ga_meeting_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int
         return ga_islands_launch(_native.C().ga_meeting, head, pop, pop_cost, G, m, r, purge_first, mutate, seed,
                                  island_base, gen_base, device)
     return ga_meeting_reference(tables, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
+
+
+# ---- simulated-annealing chains (optim.hip::sa_meeting_kernel, frame: optimize/sa.py) ------------------
+def sa_meeting_lds(M: int) -> int:
+    """Bytes of LDS per 64 chains (``avk::sa_meeting_lds``): the [3 M][64] int16 solutions, the [M][64]
+    start seconds and day bits, and the staged domain — 31,680 at M = 32."""
+    return 3 * M * 64 * 2 + 2 * M * 64 * 4 + 4 * (3 * MAX_CARD + 2 * MAX_M + 2 * MAX_Q + 5 * MAX_LIST)
+
+
+def sa_meeting_init(tables: dict, n: int, seed: int, chain_base: int) -> np.ndarray:
+    """Start schedules [n, 3 M] int16 of global chains ``chain_base ..`` (:func:`~avenir_amd.optimize.sa.sa_chains_init`)."""
+    from .sa import sa_chains_init
+    return sa_chains_init(tables["cards"], lambda s: ga_meeting_valid(tables, s), n, seed, chain_base)
+
+
+def sa_meeting_reference(tables: dict, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float,
+                         interval: int, geometric: bool, max_retry: int, seed: int, offset: int = 0, it_begin: int = 0,
+                         temp_start=None, best=None, best_cost=None, chain_base: int = 0):
+    """Host twin of ``sa_meeting_kernel``: the chain frame of :mod:`~avenir_amd.optimize.sa` with the
+    island kernel's mutation as the proposal, ``mt_valid`` and ``mt_cost``.  Returns (best int16,
+    best_cost, stats, sol int16, cost, temperature)."""
+    from .sa import SaDomain, sa_chains_reference
+    dom = SaDomain(propose=lambda s, x, y: _mutated(tables, s, x, y), valid=lambda s: ga_meeting_valid(tables, s),
+                   price=lambda s: ga_meeting_price(tables, s))
+    b, bc, st, s, c, temp = sa_chains_reference(
+        dom, np.array(sol, dtype=np.int64), cost, iters, t0, cool, interval, geometric, max_retry, seed, offset,
+        it_begin, temp_start, None if best is None else np.array(best, dtype=np.int64), best_cost, chain_base)
+    return b.astype(np.int16), bc, st, s.astype(np.int16), c, temp
+
+
+def sa_meeting_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float, interval: int,
+                   geometric: bool, max_retry: int, seed: int, device, offset: int = 0, it_begin: int = 0,
+                   temp_start=None, best=None, best_cost=None, chain_base: int = 0):
+    """Advance the chains ``iters`` moves (from move ``it_begin``) on ``device``: the kernel on the GPU,
+    the twin on the host.  ``domain`` is a MeetingScheduleDomain or its :func:`meeting_tables`.  Returns
+    numpy (best int16, best_cost, stats, sol int16, cost, temperature)."""
+    tables = domain if isinstance(domain, dict) else meeting_tables(domain)
+    if tables is None:
+        raise ValueError("the domain is outside the meeting kernel's limits")
+    device = torch.device(device)
+    if device.type == "cuda":
+        from .. import _native
+        from .sa import sa_chains_launch
+        return sa_chains_launch(_native.C().sa_meeting, tuple(_device_tables(tables, device)), (), sol, cost, iters, t0,
+                                cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, best,
+                                best_cost, chain_base, device)
+    return sa_meeting_reference(tables, sol, cost, iters, t0, cool, interval, geometric, max_retry, seed, offset,
+                                it_begin, temp_start, best, best_cost, chain_base)

@@ -16,7 +16,10 @@ Reference behaviour:
 
 MI355X design: the population / the set of chains / the set of islands is the batch axis of
 device tensors.  Simulated annealing over an :class:`AssignmentDomain` runs entirely inside one
-K22 kernel launch (one chain per lane, solution tile in LDS), and so does the island genetic
+K22 kernel launch (one chain per lane, solution tile in LDS); over meeting-schedule and
+feature-subset domains it runs in the chain kernels of optimize/sa.py (``sa_meeting_kernel``: one
+chain per lane; ``sa_subset_kernel``: 1 to 16 waves per chain over a shared row tile), whose numpy
+twins they equal bit for bit, the Metropolis decision included.  So does the island genetic
 algorithm (optimize/ga.py: one workgroup per island, pool / costs / children in LDS, all
 generations of a migration interval per launch; its numpy twin is the CPU path, bit-equal).
 Other domains take batched tensor ops per generation; the GA over them runs one generation per
@@ -33,6 +36,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
+from functools import partial
 from typing import Callable, Sequence
 
 import numpy as np
@@ -78,13 +82,44 @@ def _global_best(comm: Comm, cost: torch.Tensor, sol: torch.Tensor) -> tuple[tor
 # ================================================================================================
 # simulated annealing
 # ================================================================================================
+class _Chains:
+    """A chain engine: one of the chain kernels of optim.hip on a GPU, its host twin on the CPU.
+    ``names`` are the (GPU, CPU) engine names of ``OptResult.stats``; ``init(n, seed, chain_base)``
+    draws start solutions, ``price(sol)`` is their cost and ``run`` advances them (numpy in and out,
+    as ``ga_meeting.sa_meeting_run``)."""
+
+    def __init__(self, names, init, price, run):
+        self.names, self.init, self.price, self.run = names, init, price, run
+
+    def name(self, device) -> str:
+        return self.names[0] if device.type == "cuda" else self.names[1]
+
+    def start(self, device, n: int, seed: int, chain_base: int) -> torch.Tensor:
+        return torch.from_numpy(self.init(n, seed, chain_base).astype(np.int64)).to(device)
+
+    def cost(self, device, sol: torch.Tensor) -> torch.Tensor:
+        return torch.from_numpy(np.asarray(self.price(sol.cpu().numpy()), dtype=np.float32)).to(device)
+
+    def advance(self, device, sol, cost, iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin=0,
+                temp_start=None, best=None, best_cost=None, return_state=True, chain_base=0):
+        """The signature and the results of :func:`sa_assign` with ``return_state``, on ``device``."""
+        host = lambda t: None if t is None else t.detach().cpu().numpy()
+        b, bc, stats, s, c, temp = self.run(host(sol), host(cost), iters, t0, cool, interval, geometric, max_retry,
+                                            seed, device, offset, it_begin, temp_start, host(best), host(best_cost),
+                                            chain_base)
+        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
+        return dev(b).long(), dev(bc), stats, dev(s).long(), dev(c), float(temp)
+
+
 class SimulatedAnnealing:
     """Batched SA chains.  The one-launch K22 kernel (``sa_assign_kernel``) takes assignment domains
     with single-position moves (``max.step.size`` = 1) and L <= 512 positions (the [L][64]
-    solution tile of a wave lives in LDS).  Multi-position steps, larger L and other domains run
-    the batched generic path: every chain of the rank advances together, one set of tensor ops
-    per move (documented limit; the reference's task-schedule configurations all use step 1 and
-    tens of positions)."""
+    solution tile of a wave lives in LDS).  Meeting-schedule and feature-subset domains inside the
+    limits of their kernels take ``sa_meeting_kernel`` / ``sa_subset_kernel`` (one launch per run or
+    checkpoint segment, bit-equal host twins; :meth:`_chain_engine`).  Multi-position steps, larger
+    L and other domains run the batched generic path: every chain of the rank advances together,
+    one set of tensor ops per move (documented limit; the reference's task-schedule configurations
+    all use step 1 and tens of positions)."""
 
     def __init__(self, domain: SearchDomain, n_chains: int = 8, iters: int = 300, t0: float = 30.0,
                  cooling: float = 0.99, geometric: bool = True, interval: int = 2, step: int = 1,
@@ -116,9 +151,10 @@ class SimulatedAnnealing:
         d = self.domain
         kernel_ok = isinstance(d, AssignmentDomain) and self.step == 1 and d.L <= 512
         use_kernel = kernel_ok if self.use_kernel is None else (self.use_kernel and kernel_ok)
+        engine = None if isinstance(d, AssignmentDomain) else self._chain_engine()
         chain_base = None
-        if use_kernel:
-            best, bc, stats, gen, chain_base = self._run_kernel(comm, init)
+        if use_kernel or engine is not None:
+            best, bc, stats, gen, chain_base = self._run_kernel(comm, init, engine)
         else:
             seed = self.seed + 1_000_003 * comm.rank
             gen = _gen(d.device, seed)
@@ -141,18 +177,56 @@ class SimulatedAnnealing:
         b, c = _global_best(comm, bc, best)
         return OptResult(b, c, bc, best, stats=stats)
 
-    def _run_kernel(self, comm, init):
+    def _chain_engine(self):
+        """The one-launch chain kernel that applies to a domain other than an assignment domain, or
+        None (the generic torch path): single-position moves and no tied groups.  A
+        MeetingScheduleDomain within ``meeting_tables``' limits takes ``sa_meeting_kernel``
+        (optimize/ga_meeting.py), a FeatureSubsetDomain with the built-in naive-Bayes evaluator within
+        ``subset_tables``' limits takes ``sa_subset_kernel`` (optimize/ga_subset.py) — on a GPU by
+        default, on the CPU (their host twins) only when ``use_kernel`` is True, so CPU default
+        results are unchanged.  Measured against the generic path on one MI355X
+        (profiles/sa_domains_bench.jsonl, 300 moves, whole runs): meetings 66 x / 53 x / 15 x faster
+        at 1 / 64 / 4,096 chains, subsets 47 x / 47 x / 27 x at 4,000 rows and 4.0 x / 4.6 x / 5.6 x at
+        65,536 rows for 1 / 64 / 1,024 chains.  One subset chain is one workgroup that streams every
+        row once per move, so a single chain loses above 2^17 rows
+        (profiles/sa_subset_cap_sweep.jsonl): past ``ga_subset.SA_ROW_CAP`` the default stays
+        generic and ``use_kernel=True`` still forces the engine.  The state of a chain is explicit,
+        so the engines work with ``recovery``."""
+        d = self.domain
+        if self.use_kernel is False or self.step != 1 or getattr(d, "groups", None):
+            return None
+        if not (self.use_kernel is True or d.device.type == "cuda"):
+            return None
+        from . import ga_meeting as gm, ga_subset as gs
+        tb = gm.meeting_tables(d)           # None unless a MeetingScheduleDomain within the kernel's limits
+        if tb is not None and gm.sa_meeting_lds(tb["M"]) <= 64 * 1024:
+            return _Chains(("sa_meeting_kernel", "sa_meeting_twin"), partial(gm.sa_meeting_init, tb),
+                           partial(gm.ga_meeting_price, tb), partial(gm.sa_meeting_run, tb))
+        if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3:
+            tb = gs.subset_tables(d)        # None unless a FeatureSubsetDomain with the built-in evaluator
+            # one chain is one workgroup streaming every row once per move: by default up to
+            # ga_subset.SA_ROW_CAP rows, where a single chain still beats the generic path
+            if tb is not None and (self.use_kernel is True or tb["N"] <= gs.SA_ROW_CAP):
+                return _Chains(("sa_subset_kernel", "sa_subset_host"), partial(gs.sa_subset_init, tb),
+                               lambda s: gs.ga_subset_price(tb, gs.pack_masks(s), d.device),
+                               partial(gs.sa_subset_run, tb))
+        return None
+
+    def _run_kernel(self, comm, init, engine=None):
         """K22 path.  Chains are GLOBAL: chain ``g`` draws Philox stream ``(seed, g)`` and starts from
         row ``g`` of one population drawn from ``seed`` alone, rank ``r`` runs chains
         ``[r * n_chains, (r + 1) * n_chains)``.  The W-rank result therefore equals one process
         running ``W * n_chains`` chains, and the checkpoint (rank 0 writes every chain) resumes at
         ANY world size: the restored chains are re-dealt by global index.  Under checkpointing the
         run is split into segments of ``segment`` moves (one launch each, same Philox counters and
-        cooling schedule as one launch)."""
+        cooling schedule as one launch).  ``engine`` (:meth:`_chain_engine`) supplies the start
+        solutions, their price and the launch for a meeting-schedule or feature-subset domain;
+        without it the domain is an assignment domain (``sa_assign``)."""
         from ..data.table import shard_range
         d = self.domain
         W, r = comm.world, comm.rank
         gen = None                                               # local search: per global chain (run)
+        advance = partial(sa_assign, d) if engine is None else partial(engine.advance, d.device)
         stats = {"better": 0, "worse_accepted": 0, "rejected": 0}
         best = bc = temp = None
         b0 = 0
@@ -168,21 +242,26 @@ class SimulatedAnnealing:
             else:
                 if init is None:
                     total = self.n_chains * W
-                    sol = d.random(total, _gen(d.device, self.seed))[0][r * self.n_chains:(r + 1) * self.n_chains]
                     a = r * self.n_chains
+                    if engine is None:
+                        sol = d.random(total, _gen(d.device, self.seed))[0][a:a + self.n_chains]
+                    else:                                        # per global chain: no rank draws the others'
+                        sol = engine.start(d.device, self.n_chains, self.seed, a)
                 else:
                     sol = init.to(d.device).long().clone()
                     counts = comm.all_gather(torch.tensor([sol.shape[0]])).view(-1).tolist()
                     total, a = sum(counts), sum(counts[:r])
-                cost = d.evaluate(sol)
+                # the engines price with their own arithmetic: the current cost is always the kernel's
+                # price of the solution, the same bits on either device
+                cost = d.evaluate(sol) if engine is None else engine.cost(d.device, sol)
             seg = max(1, self.segment or -(-self.iters // 10)) if lp.enabled else max(1, self.iters)
             for b in range(b0, self.iters, seg):
                 n = min(seg, self.iters - b)
                 with lp.step(b // seg):
-                    best, bc, s, sol, cost, temp = sa_assign(d, sol, cost, n, self.t0, self.cooling, self.interval,
-                                                             self.geometric, self.max_retry, self.seed, 0, it_begin=b,
-                                                             temp_start=temp, best=best, best_cost=bc,
-                                                             return_state=True, chain_base=a)
+                    best, bc, s, sol, cost, temp = advance(sol, cost, n, self.t0, self.cooling, self.interval,
+                                                           self.geometric, self.max_retry, self.seed, 0, it_begin=b,
+                                                           temp_start=temp, best=best, best_cost=bc,
+                                                           return_state=True, chain_base=a)
                 for k in stats:
                     stats[k] += s[k]
                 if lp.enabled:
@@ -192,7 +271,10 @@ class SimulatedAnnealing:
                                "chains": total}, force=True)
         if best is None:                                   # no moves at all
             best, bc = sol.clone(), cost.clone()
-        return best.long(), bc, self._global_stats(comm, stats), gen, a
+        stats = self._global_stats(comm, stats)
+        if engine is not None:
+            stats["engine"] = engine.name(d.device)
+        return best.long(), bc, stats, gen, a
 
     @staticmethod
     def _global_stats(comm, stats: dict) -> dict:

@@ -1,0 +1,299 @@
+"""Simulated-annealing chains over a meeting-schedule domain as one K22 launch
+(csrc/kernels/optim.hip::sa_meeting_kernel) and the chain frame's numpy twin (optimize/sa.py,
+optimize/ga_meeting.py): sa_exp against float64 exp, segmented runs and global chain indexing,
+invariants, branch coverage, edge shapes, dispatch and recovery in SimulatedAnnealing; on the GPU the
+kernel bit-equal to the twin (the Metropolis decision included), the class equal on both devices, and
+the binding's validation."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from avenir_amd.optimize.domains import MeetingScheduleDomain
+from tests._dist import run_world_outcome
+
+
+@functools.lru_cache(maxsize=None)
+def _instance(M, Q, seed):
+    from avenir_amd.optimize.ga_meeting import meeting_tables
+    d = MeetingScheduleDomain.random_instance(M, Q, seed=seed)
+    return d, meeting_tables(d)
+
+
+@functools.lru_cache(maxsize=None)
+def _one_minute():
+    from avenir_amd.optimize.ga_meeting import meeting_tables
+    src = MeetingScheduleDomain.random_instance(5, 10, seed=0)
+    parts = [src.member[:, i].nonzero().view(-1).tolist() for i in range(5)]
+    d = MeetingScheduleDomain(parts, (src.dur / 60).tolist(), 10, src.ordered, src.blocked, src.role_w.tolist(),
+                              minutes=(0,))
+    return d, meeting_tables(d)
+
+
+def _start(tb, n, seed, base):
+    from avenir_amd.optimize.ga_meeting import ga_meeting_price, sa_meeting_init
+    sol = sa_meeting_init(tb, n, seed, base)
+    return sol, ga_meeting_price(tb, sol)
+
+
+def _state_equal(a, b):
+    """(best, best_cost, stats, sol, cost, temperature) bit for bit."""
+    for i in (0, 1, 3, 4):
+        assert a[i].dtype == b[i].dtype and np.array_equal(a[i], b[i]), i
+    assert a[2] == b[2]
+    assert np.float32(a[5]).view(np.uint32) == np.float32(b[5]).view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------- CPU
+def _exp_grid():
+    """Fixed grid over [-87, 0]: 2^20 + 1 even steps, powers of two down to 2^-40 next to 0, the
+    neighbours of every multiple of ln 2 / 2 (where k = rint(x log2 e) changes) and the ends."""
+    even = np.linspace(-87.0, 0.0, (1 << 20) + 1)
+    near0 = -np.exp2(-np.arange(0, 41, dtype=np.float64))
+    half = -np.arange(0, 252) * (np.log(2.0) / 2.0)
+    half = half[half >= -87.0].astype(np.float32)
+    edges = np.concatenate([np.nextafter(half, np.float32(-100)), half, np.nextafter(half, np.float32(1))])
+    x = np.concatenate([even, near0, edges.astype(np.float64), [-87.0, 0.0]]).astype(np.float32)
+    return np.unique(x[(x <= 0) & (x >= -87)])
+
+
+def test_sa_exp_against_float64_exp():
+    from avenir_amd.optimize.sa import sa_exp
+    x = _exp_grid()
+    assert x[0] == -87 and x[-1] == 0 and (x > -1e-9).sum() > 10
+    got = sa_exp(x)
+    assert got.dtype == np.float32
+    rel = np.abs(got.astype(np.float64) / np.exp(x.astype(np.float64)) - 1.0)
+    print(f"sa_exp on {x.size} points of [-87, 0]: max relative error {rel.max():.3g}")
+    assert rel.max() <= 1e-6
+    assert sa_exp(np.float32(0.0)) == np.float32(1.0)
+    assert (np.diff(got) >= 0).all()                                  # monotone on the grid (x ascending)
+    low = sa_exp(np.array([-87.0, -87.5, -1000.0, -3e38, -np.inf], dtype=np.float32))
+    assert not np.isnan(low).any() and (low == low[0]).all() and low[0] > 0
+
+
+@pytest.mark.parametrize("geometric", [True, False])
+def test_twin_segments_equal_one_run(geometric):
+    from avenir_amd.optimize.ga_meeting import sa_meeting_reference
+    _, tb = _instance(10, 20, 3)
+    sol, cost = _start(tb, 24, 7, 11)
+    cool = 0.97 if geometric else 1e-4
+    args = (0.05, cool, 3, geometric, 3, 7)
+    one = sa_meeting_reference(tb, sol, cost, 300, *args, chain_base=11)
+    st = None
+    total = {"better": 0, "worse_accepted": 0, "rejected": 0}
+    s, c, best, bc, temp = sol, cost, None, None, None
+    for b in range(0, 300, 70):
+        st = sa_meeting_reference(tb, s, c, min(70, 300 - b), *args, it_begin=b, temp_start=temp, best=best,
+                                  best_cost=bc, chain_base=11)
+        best, bc, _, s, c, temp = st
+        for k in total:
+            total[k] += st[2][k]
+    _state_equal(one, (best, bc, total, s, c, temp))
+    assert one[0].dtype == np.int16 and one[1].dtype == np.float32 and one[3].dtype == np.int16
+    if not geometric:                                                 # max(t0 - 300 * cool, 1e-12) in fp32
+        assert np.float32(one[5]) == np.float32(np.float32(0.05) - np.float32(np.float32(300) * np.float32(1e-4)))
+
+
+def test_chain_indexing_is_global():
+    """Chains [3, 8) run alone equal rows 3..7 of chains [0, 8), starts included."""
+    from avenir_amd.optimize.ga_meeting import sa_meeting_reference
+    _, tb = _instance(10, 20, 3)
+    sol, cost = _start(tb, 8, 21, 0)
+    part_sol, part_cost = _start(tb, 5, 21, 3)
+    assert np.array_equal(part_sol, sol[3:]) and np.array_equal(part_cost, cost[3:])
+    full = sa_meeting_reference(tb, sol, cost, 60, 0.05, 0.97, 3, True, 3, 21)
+    part = sa_meeting_reference(tb, part_sol, part_cost, 60, 0.05, 0.97, 3, True, 3, 21, chain_base=3)
+    for i in (0, 1, 3, 4):
+        assert np.array_equal(full[i][3:], part[i])
+    assert full[5] == part[5]
+
+
+@functools.lru_cache(maxsize=None)
+def _branch_run():
+    from avenir_amd.optimize.ga_meeting import sa_meeting_reference
+    _, tb = _instance(10, 20, 3)
+    sol, cost = _start(tb, 128, 5, 0)
+    return sol, cost, sa_meeting_reference(tb, sol, cost, 200, 0.05, 0.97, 3, True, 3, 5)
+
+
+def test_every_branch_is_taken_and_invariants_hold():
+    from avenir_amd.optimize.ga_meeting import ga_meeting_price, ga_meeting_valid
+    d, tb = _instance(10, 20, 3)
+    sol, cost, (best, bc, st, cur, cc, temp) = _branch_run()
+    no_move = 128 * 200 - sum(st.values())
+    print(st, "no-move", no_move)
+    assert min(st.values()) > 0 and no_move > 0
+    # the counters sum to the moves that had a valid candidate, counted here by the pricing calls
+    from avenir_amd.optimize.ga_meeting import _mutated
+    from avenir_amd.optimize.sa import SaDomain, sa_chains_reference
+    priced = [0]
+
+    def price(s):
+        priced[0] += s.shape[0]
+        return ga_meeting_price(tb, s)
+
+    dom = SaDomain(lambda s, x, y: _mutated(tb, s, x, y), lambda s: ga_meeting_valid(tb, s), price)
+    again = sa_chains_reference(dom, sol.astype(np.int64), cost, 200, 0.05, 0.97, 3, True, 3, 5)
+    assert again[2] == st and sum(st.values()) == priced[0] == 128 * 200 - no_move
+    assert (bc <= cost).all() and (bc <= cc).all()
+    assert np.array_equal(ga_meeting_price(tb, cur), cc) and np.array_equal(ga_meeting_price(tb, best), bc)
+    for s, c in ((best, bc), (cur, cc)):
+        assert ga_meeting_valid(tb, s[np.isfinite(c)]).all()
+    ref = d.evaluate(torch.from_numpy(best.astype(np.int64))).numpy()
+    fin = np.isfinite(bc)
+    assert fin.any() and np.array_equal(np.isfinite(ref), fin)
+    assert (np.abs(bc[fin] - ref[fin]) <= 1e-5 * np.abs(ref[fin])).all()
+
+
+@pytest.mark.parametrize("case", ["M1", "M32_Q64", "one_minute"])
+def test_twin_edge_shapes(case):
+    from avenir_amd.optimize.ga_meeting import ga_meeting_price, ga_meeting_valid, sa_meeting_reference
+    _, tb = {"M1": lambda: _instance(1, 3, 0), "M32_Q64": lambda: _instance(32, 64, 2), "one_minute": _one_minute}[case]()
+    sol, cost = _start(tb, 48, 4, 0)
+    if case == "M32_Q64":                                             # inf-cost chains are exercised
+        assert np.isinf(cost).any() and np.isfinite(cost).any()
+    best, bc, st, cur, cc, temp = sa_meeting_reference(tb, sol, cost, 40, 0.05, 0.97, 3, True, 3, 4)
+    assert (cur >= 0).all() and (cur < tb["cards"]).all() and (best >= 0).all() and (best < tb["cards"]).all()
+    assert np.array_equal(ga_meeting_price(tb, cur), cc) and np.array_equal(ga_meeting_price(tb, best), bc)
+    assert ga_meeting_valid(tb, cur[np.isfinite(cc)]).all() and (bc <= cost).all()
+    assert sum(st.values()) <= 48 * 40 and st["better"] > 0
+    if case == "one_minute":
+        assert tb["cards"][2] == 1 and (cur[:, 2::3] == 0).all()
+    if case == "M32_Q64":
+        assert (np.isfinite(cc) >= np.isfinite(cost)).all()           # a valid chain never turns invalid
+
+
+def test_dispatch_on_the_cpu():
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    d, _ = _instance(6, 10, 1)
+    kw = dict(n_chains=6, iters=40, t0=0.05, cooling=0.97, interval=3, seed=5)
+    twin = SimulatedAnnealing(d, use_kernel=True, **kw).run()
+    assert twin.stats.get("engine") == "sa_meeting_twin"
+    assert np.isfinite(twin.best_cost) and bool(d.valid(twin.best.view(1, -1))[0])
+    assert float(d.cost(twin.best.view(1, -1))[0]) == pytest.approx(float(twin.best_cost), rel=1e-5)
+    assert twin.costs.shape == (6,) and twin.solutions.shape == (6, 18)
+    assert sum(v for k, v in twin.stats.items() if k != "engine") <= 6 * 40
+    default = SimulatedAnnealing(d, **kw).run()
+    generic = SimulatedAnnealing(d, use_kernel=False, **kw).run()
+    assert "engine" not in default.stats and "engine" not in generic.stats
+    assert torch.equal(default.best, generic.best) and default.best_cost == generic.best_cost
+    assert torch.equal(default.costs, generic.costs) and default.stats == generic.stats
+    # outside the kernel's limits or with multi-position steps: the generic path even when asked for the kernel
+    big = MeetingScheduleDomain.random_instance(33, 40, seed=0)
+    assert SimulatedAnnealing(big, use_kernel=True, **kw)._chain_engine() is None
+    assert "engine" not in SimulatedAnnealing(big, use_kernel=True, **dict(kw, iters=2)).run().stats
+    assert SimulatedAnnealing(d, use_kernel=True, step=2, **kw)._chain_engine() is None
+    assert "engine" not in SimulatedAnnealing(d, use_kernel=True, step=2, **dict(kw, iters=2)).run().stats
+
+
+def _annealing_meeting(rank, world, ckdir):
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    from avenir_amd.utils.resilience import RecoveryConfig
+    d = MeetingScheduleDomain.random_instance(6, 10, seed=1)
+    r = SimulatedAnnealing(d, n_chains=8 // world, iters=60, t0=0.05, cooling=0.97, interval=3, seed=1,
+                           use_kernel=True, recovery=RecoveryConfig(ckdir), segment=10).run()
+    return r.best_cost, r.best.tolist(), r.costs.tolist(), r.stats
+
+
+def test_fault_then_fresh_resume_equals_uninterrupted(tmp_path):
+    """The pattern of tests/test_recovery.py: rank 1 exits at the start of segment 3, fresh processes
+    resume from the checkpoint and end where the uninterrupted run ends."""
+    fault = {"AVMI_FAULT_RANK": "1", "AVMI_FAULT_ITER": "3", "AVMI_FAULT_MODE": "exit"}
+    clean, errs, codes = run_world_outcome(_annealing_meeting, 2, str(tmp_path / "clean"))
+    assert not errs and codes == [0, 0], errs
+    assert clean[0][3]["engine"] == "sa_meeting_twin"
+    ck = str(tmp_path / "faulty")
+    res, errs, codes = run_world_outcome(_annealing_meeting, 2, ck, env=fault, timeout=90)
+    assert codes[1] == 17 and len(res) < 2, (codes, errs)
+    assert list((tmp_path / "faulty").glob("*.ckpt")), "no checkpoint was committed before the fault"
+    resumed, errs, codes = run_world_outcome(_annealing_meeting, 2, ck)
+    assert not errs and codes == [0, 0], errs
+    assert resumed == clean
+
+
+# ------------------------------------------------------------------------------------------- GPU
+_SHAPES = {"reference": (10, 20, 3), "smallest": (1, 3, 0), "largest": (32, 64, 2)}
+_MOVES = {1: 150, 65: 60, 4096: 12}          # moves by chain count: the twin stays within seconds
+
+
+@functools.lru_cache(maxsize=None)
+def _twin_run(shape, chains, geometric, max_retry):
+    from avenir_amd.optimize.ga_meeting import sa_meeting_reference
+    _, tb = _instance(*_SHAPES[shape])
+    sol, cost = _start(tb, chains, 5, 100)
+    cool = 0.97 if geometric else 2e-4
+    return sol, cost, cool, sa_meeting_reference(tb, sol, cost, _MOVES[chains], 0.05, cool, 3, geometric, max_retry, 5,
+                                                 offset=17, chain_base=100)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_retry", [0, 3])
+@pytest.mark.parametrize("geometric", [True, False])
+@pytest.mark.parametrize("chains", [1, 65, 4096])
+@pytest.mark.parametrize("shape", sorted(_SHAPES))
+def test_kernel_bit_equal_to_twin(cuda, shape, chains, geometric, max_retry):
+    from avenir_amd.optimize.ga_meeting import sa_meeting_run
+    _, tb = _instance(*_SHAPES[shape])
+    sol, cost, cool, want = _twin_run(shape, chains, geometric, max_retry)
+    got = sa_meeting_run(tb, sol, cost, _MOVES[chains], 0.05, cool, 3, geometric, max_retry, 5, torch.device("cuda"),
+                         offset=17, chain_base=100)
+    print(shape, chains, want[2])
+    _state_equal(want, got)
+
+
+@pytest.mark.gpu
+def test_two_chained_launches_equal_one_twin_run(cuda):
+    from avenir_amd.optimize.ga_meeting import sa_meeting_reference, sa_meeting_run
+    d, tb = _instance(10, 20, 3)
+    sol, cost = _start(tb, 70, 9, 40)
+    want = sa_meeting_reference(tb, sol, cost, 90, 0.05, 0.97, 3, True, 3, 9, chain_base=40)
+    dev = torch.device("cuda")
+    a = sa_meeting_run(d, sol, cost, 35, 0.05, 0.97, 3, True, 3, 9, dev, chain_base=40)
+    b = sa_meeting_run(d, a[3], a[4], 55, 0.05, 0.97, 3, True, 3, 9, dev, it_begin=35, temp_start=a[5], best=a[0],
+                       best_cost=a[1], chain_base=40)
+    total = {k: a[2][k] + b[2][k] for k in a[2]}
+    _state_equal(want, (b[0], b[1], total, b[3], b[4], b[5]))
+
+
+@pytest.mark.gpu
+def test_simulated_annealing_gpu_equals_cpu(cuda):
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    kw = dict(n_chains=40, iters=80, t0=0.05, cooling=0.97, interval=3, seed=9, locally_optimize=False)
+    rc = SimulatedAnnealing(MeetingScheduleDomain.random_instance(10, 20, seed=3), use_kernel=True, **kw).run()
+    rg = SimulatedAnnealing(MeetingScheduleDomain.random_instance(10, 20, seed=3, device="cuda"), **kw).run()
+    assert rg.stats["engine"] == "sa_meeting_kernel" and rc.stats["engine"] == "sa_meeting_twin"   # the GPU default
+    assert rg.best_cost == rc.best_cost and torch.equal(rg.best.cpu(), rc.best)
+    assert torch.equal(rg.costs.cpu(), rc.costs) and torch.equal(rg.solutions.cpu(), rc.solutions)
+    assert {k: v for k, v in rg.stats.items() if k != "engine"} == {k: v for k, v in rc.stats.items() if k != "engine"}
+    assert np.isfinite(rg.best_cost)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["index", "M33", "max_retry"])
+def test_binding_validation(cuda, case):
+    """Each violation raises before anything is launched: every tensor stays as it was."""
+    from avenir_amd import _native
+    from avenir_amd.optimize.ga_meeting import _device_tables
+    _, tb = _instance(10, 20, 3)
+    dev = torch.device("cuda")
+    sol, cost = _start(tb, 6, 1, 0)
+    dom = list(_device_tables(tb, dev))
+    max_retry = -1 if case == "max_retry" else 3
+    if case == "index":
+        sol = sol.copy()
+        sol[4, 4] = tb["cards"][4]                                   # an hour index one past its table
+    if case == "M33":
+        dom[3] = torch.full((33,), 1800, dtype=torch.int32, device=dev)      # dur of 33 meetings
+        dom[4] = torch.zeros(33, dtype=torch.int32, device=dev)
+        sol = np.zeros((6, 99), dtype=np.int16)
+    ts, tc = torch.from_numpy(sol).to(dev), torch.from_numpy(cost).to(dev)
+    tb_, tbc = ts.clone(), tc.clone()
+    st = torch.zeros(4, dtype=torch.long, device=dev)
+    keep = ts.clone(), tc.clone()
+    with pytest.raises((RuntimeError, ValueError)):
+        _native.C().sa_meeting(*dom, ts, tc, tb_, tbc, 5, 0.05, 0.97, 3, True, max_retry, 1, 0, st, 0, 0.05, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(ts, keep[0]) and torch.equal(tc, keep[1]) and torch.equal(tb_, keep[0])
+    assert torch.equal(tbc, keep[1]) and bool((st == 0).all())

@@ -1,0 +1,314 @@
+"""Simulated-annealing chains over feature subsets scored by naive Bayes as one K22 launch
+(csrc/kernels/optim.hip::sa_subset_kernel) and the chain frame's numpy twin (optimize/sa.py,
+optimize/ga_subset.py): segmented runs and global chain indexing, invariants, branch coverage, edge
+shapes, dispatch and recovery in SimulatedAnnealing; on the GPU the kernel bit-equal to the twin for
+every split of the workgroup into chains, the class equal on both devices, and the binding's
+validation."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from avenir_amd.optimize.domains import FeatureSubsetDomain
+from tests._dist import run_world_outcome
+
+
+@functools.lru_cache(maxsize=None)
+def _random(N, F, C, seed=0):
+    """Random fp32 log-likelihoods whose labels follow the first features (so subsets differ in error)."""
+    rng = np.random.default_rng(77 + 1000 * seed + 100 * F + C)
+    LL = (-8.0 * rng.random((N, F, C))).astype(np.float32)
+    prior = np.log(rng.dirichlet(np.full(C, 5.0))).astype(np.float32)
+    labels = (LL[:, : max(1, F // 3), :].sum(1) + rng.normal(0, 2.0, (N, C))).argmax(1)
+    labels[0] = C - 1
+    return LL, prior, labels
+
+
+def _domain(data, device="cpu", **kw):
+    LL, prior, labels = data
+    return FeatureSubsetDomain(LL.shape[1], loglik=torch.from_numpy(LL), log_prior=torch.from_numpy(prior),
+                               labels=torch.from_numpy(labels), device=device, **kw)
+
+
+_CASES = {  # N, F, C, min_size, max_size
+    "reference": (517, 12, 3, 2, 8),
+    "smallest": (1, 1, 2, 0, 1),
+    "short_tile": (300, 32, 16, 1, 32),        # F C = 512: the tile is shorter than a wave
+    "ragged_tiles": (4133, 5, 2, 1, 5),        # several tiles and a ragged last one
+    "fixed_size": (517, 12, 3, 5, 5),          # every flip leaves the size range
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _tables(case):
+    from avenir_amd.optimize.ga_subset import subset_tables
+    N, F, C, lo, hi = _CASES[case]
+    d = _domain(_random(N, F, C), min_size=lo, max_size=hi)
+    tb = subset_tables(d)
+    assert tb is not None
+    return d, tb
+
+
+def _start(tb, n, seed, base):
+    from avenir_amd.optimize.ga_subset import ga_subset_price, pack_masks, sa_subset_init
+    sol = sa_subset_init(tb, n, seed, base)
+    return sol, ga_subset_price(tb, pack_masks(sol))
+
+
+def _state_equal(a, b):
+    """(best, best_cost, stats, sol, cost, temperature) bit for bit."""
+    for i in (0, 1, 3, 4):
+        assert a[i].dtype == b[i].dtype and np.array_equal(a[i], b[i]), i
+    assert a[2] == b[2]
+    assert np.float32(a[5]).view(np.uint32) == np.float32(b[5]).view(np.uint32)
+
+
+def _check(d, tb, sol, cost):
+    """0 / 1 rows; every cost = errors / N through the domain's own errors(); finite < 1 costs are valid."""
+    from avenir_amd.optimize.ga_subset import ga_subset_valid, pack_masks
+    assert sol.dtype == np.int16 and cost.dtype == np.float32 and ((sol == 0) | (sol == 1)).all()
+    ok = ga_subset_valid(tb, pack_masks(sol))
+    err = d.errors(torch.from_numpy(sol.astype(np.int64))).numpy()
+    want = np.where(ok, err.astype(np.float32) / np.float32(tb["N"]), np.float32(1.0)).astype(np.float32)
+    assert np.array_equal(cost, want)
+
+
+# ------------------------------------------------------------------------------------------- CPU
+@pytest.mark.parametrize("geometric", [True, False])
+def test_twin_segments_equal_one_run(geometric):
+    from avenir_amd.optimize.ga_subset import sa_subset_reference
+    _, tb = _tables("reference")
+    sol, cost = _start(tb, 24, 7, 11)
+    args = (0.05, 0.97 if geometric else 1e-4, 3, geometric, 3, 7)
+    one = sa_subset_reference(tb, sol, cost, 300, *args, chain_base=11)
+    total = {"better": 0, "worse_accepted": 0, "rejected": 0}
+    s, c, best, bc, temp = sol, cost, None, None, None
+    for b in range(0, 300, 70):
+        st = sa_subset_reference(tb, s, c, min(70, 300 - b), *args, it_begin=b, temp_start=temp, best=best,
+                                 best_cost=bc, chain_base=11)
+        best, bc, _, s, c, temp = st
+        for k in total:
+            total[k] += st[2][k]
+    _state_equal(one, (best, bc, total, s, c, temp))
+
+
+def test_chain_indexing_is_global():
+    """Chains [3, 8) run alone equal rows 3..7 of chains [0, 8), starts included."""
+    from avenir_amd.optimize.ga_subset import sa_subset_reference
+    _, tb = _tables("reference")
+    sol, cost = _start(tb, 8, 21, 0)
+    part_sol, part_cost = _start(tb, 5, 21, 3)
+    assert np.array_equal(part_sol, sol[3:]) and np.array_equal(part_cost, cost[3:])
+    full = sa_subset_reference(tb, sol, cost, 60, 0.05, 0.97, 3, True, 3, 21)
+    part = sa_subset_reference(tb, part_sol, part_cost, 60, 0.05, 0.97, 3, True, 3, 21, chain_base=3)
+    for i in (0, 1, 3, 4):
+        assert np.array_equal(full[i][3:], part[i])
+    assert full[5] == part[5]
+
+
+def test_every_branch_is_taken_and_invariants_hold():
+    from avenir_amd.optimize.ga_subset import sa_subset_reference
+    d, tb = _tables("reference")
+    sol, cost = _start(tb, 128, 5, 0)
+    best, bc, st, cur, cc, temp = sa_subset_reference(tb, sol, cost, 200, 0.05, 0.97, 3, True, 3, 5)
+    no_move = 128 * 200 - sum(st.values())
+    print(st, "no-move", no_move)
+    assert min(st.values()) > 0 and no_move > 0
+    assert (bc <= cost).all() and (bc <= cc).all() and (bc < cost).any()
+    _check(d, tb, best, bc)
+    _check(d, tb, cur, cc)
+    assert (cc < 1.0).all()                                            # valid starts stay valid
+
+
+@pytest.mark.parametrize("case", ["smallest", "short_tile", "fixed_size"])
+def test_twin_edge_shapes(case):
+    from avenir_amd.optimize.ga_subset import sa_subset_reference
+    d, tb = _tables(case)
+    sol, cost = _start(tb, 16, 4, 0)
+    best, bc, st, cur, cc, temp = sa_subset_reference(tb, sol, cost, 30, 0.05, 0.97, 3, True, 3, 4)
+    _check(d, tb, best, bc)
+    _check(d, tb, cur, cc)
+    assert (bc <= cost).all()
+    if case == "fixed_size":       # every flip is invalid: every move is a no-move, all counters stay 0
+        assert st == {"better": 0, "worse_accepted": 0, "rejected": 0}
+        assert np.array_equal(cur, sol) and np.array_equal(cc, cost) and np.array_equal(best, sol)
+        assert np.float32(temp) == _cooled(10)                         # the schedule runs on: 30 moves, interval 3
+    else:
+        assert 0 < sum(st.values()) <= 16 * 30
+
+
+def _cooled(n):
+    t = np.float32(0.05)
+    for _ in range(n):
+        t = np.float32(t * np.float32(0.97))
+    return t
+
+
+def test_dispatch_on_the_cpu():
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    d, _ = _tables("reference")
+    kw = dict(n_chains=6, iters=40, t0=0.05, cooling=0.97, interval=3, seed=5)
+    twin = SimulatedAnnealing(d, use_kernel=True, **kw).run()
+    assert twin.stats.get("engine") == "sa_subset_host"
+    assert bool(d.valid(twin.best.view(1, -1))[0])
+    assert np.float32(float(d.errors(twin.best.view(1, -1))[0])) / np.float32(517) == np.float32(twin.best_cost)
+    assert twin.costs.shape == (6,) and twin.solutions.shape == (6, 12)
+    default = SimulatedAnnealing(d, **kw).run()
+    generic = SimulatedAnnealing(d, use_kernel=False, **kw).run()
+    assert "engine" not in default.stats and "engine" not in generic.stats
+    assert torch.equal(default.best, generic.best) and default.best_cost == generic.best_cost
+    assert torch.equal(default.costs, generic.costs) and default.stats == generic.stats
+    # tied groups, a cost callback, multi-position steps: the generic path even when asked for the kernel
+    data = _random(517, 12, 3)
+    grouped = _domain(data, min_size=2, max_size=8, groups=[[0, 1]])
+    assert SimulatedAnnealing(grouped, use_kernel=True, **kw)._chain_engine() is None
+    callback = _domain(data, min_size=2, max_size=8, cost_fn=lambda sol: sol.float().mean(1))
+    assert SimulatedAnnealing(callback, use_kernel=True, **kw)._chain_engine() is None
+    assert "engine" not in SimulatedAnnealing(callback, use_kernel=True, **dict(kw, iters=2)).run().stats
+    assert SimulatedAnnealing(d, use_kernel=True, step=2, **kw)._chain_engine() is None
+    assert "engine" not in SimulatedAnnealing(d, use_kernel=True, step=2, **dict(kw, iters=2)).run().stats
+
+
+def _annealing_subset(rank, world, ckdir):
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    from avenir_amd.utils.resilience import RecoveryConfig
+    d = _domain(_random(517, 12, 3), min_size=2, max_size=8)
+    r = SimulatedAnnealing(d, n_chains=8 // world, iters=60, t0=0.05, cooling=0.97, interval=3, seed=1,
+                           use_kernel=True, recovery=RecoveryConfig(ckdir), segment=10).run()
+    return r.best_cost, r.best.tolist(), r.costs.tolist(), r.stats
+
+
+def test_fault_then_fresh_resume_equals_uninterrupted(tmp_path):
+    """The pattern of tests/test_recovery.py: rank 1 exits at the start of segment 3, fresh processes
+    resume from the checkpoint and end where the uninterrupted run ends."""
+    fault = {"AVMI_FAULT_RANK": "1", "AVMI_FAULT_ITER": "3", "AVMI_FAULT_MODE": "exit"}
+    clean, errs, codes = run_world_outcome(_annealing_subset, 2, str(tmp_path / "clean"))
+    assert not errs and codes == [0, 0], errs
+    assert clean[0][3]["engine"] == "sa_subset_host"
+    ck = str(tmp_path / "faulty")
+    res, errs, codes = run_world_outcome(_annealing_subset, 2, ck, env=fault, timeout=90)
+    assert codes[1] == 17 and len(res) < 2, (codes, errs)
+    assert list((tmp_path / "faulty").glob("*.ckpt")), "no checkpoint was committed before the fault"
+    resumed, errs, codes = run_world_outcome(_annealing_subset, 2, ck)
+    assert not errs and codes == [0, 0], errs
+    assert resumed == clean
+
+
+# ------------------------------------------------------------------------------------------- GPU
+_GPU_CASES = ["reference", "smallest", "short_tile", "ragged_tiles"]
+_MOVES = {1: 150, 65: 60, 4096: 6}           # moves by chain count: the twin stays within seconds
+
+
+@functools.lru_cache(maxsize=None)
+def _twin_run(case, chains, geometric, max_retry):
+    from avenir_amd.optimize.ga_subset import sa_subset_reference
+    _, tb = _tables(case)
+    sol, cost = _start(tb, chains, 5, 100)
+    cool = 0.97 if geometric else 2e-4
+    return sol, cost, cool, sa_subset_reference(tb, sol, cost, _MOVES[chains], 0.05, cool, 3, geometric, max_retry, 5,
+                                                offset=17, chain_base=100)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_retry", [0, 3])
+@pytest.mark.parametrize("geometric", [True, False])
+@pytest.mark.parametrize("chains", [1, 65, 4096])
+@pytest.mark.parametrize("case", _GPU_CASES)
+def test_kernel_bit_equal_to_twin(cuda, case, chains, geometric, max_retry):
+    from avenir_amd.optimize.ga_subset import sa_subset_run
+    _, tb = _tables(case)
+    sol, cost, cool, want = _twin_run(case, chains, geometric, max_retry)
+    got = sa_subset_run(tb, sol, cost, _MOVES[chains], 0.05, cool, 3, geometric, max_retry, 5, torch.device("cuda"),
+                        offset=17, chain_base=100)
+    print(case, chains, want[2])
+    _state_equal(want, got)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", _GPU_CASES + ["fixed_size"])
+def test_waves_per_chain_changes_nothing(cuda, case):
+    """1 wave per chain (256 or 1,024 threads, 4 or 16 chains per workgroup) and 16 waves per chain
+    (1,024 threads, one chain per workgroup) both equal the twin."""
+    from avenir_amd.optimize.ga_subset import sa_subset_run
+    _, tb = _tables(case)
+    if case == "fixed_size":
+        from avenir_amd.optimize.ga_subset import sa_subset_reference
+        sol, cost = _start(tb, 65, 5, 100)
+        want = sa_subset_reference(tb, sol, cost, 20, 0.05, 0.97, 3, True, 3, 5, offset=17, chain_base=100)
+        moves, cool = 20, 0.97
+        assert sum(want[2].values()) == 0
+    else:
+        sol, cost, cool, want = _twin_run(case, 65, True, 3)
+        moves = _MOVES[65]
+    for w in (1, 16):
+        got = sa_subset_run(tb, sol, cost, moves, 0.05, cool, 3, True, 3, 5, torch.device("cuda"), offset=17,
+                            chain_base=100, waves_per_chain=w)
+        _state_equal(want, got)
+
+
+@pytest.mark.gpu
+def test_two_chained_launches_equal_one_twin_run(cuda):
+    from avenir_amd.optimize.ga_subset import sa_subset_reference, sa_subset_run
+    d, tb = _tables("ragged_tiles")
+    sol, cost = _start(tb, 70, 9, 40)
+    want = sa_subset_reference(tb, sol, cost, 90, 0.05, 0.97, 3, True, 3, 9, chain_base=40)
+    dev = torch.device("cuda")
+    a = sa_subset_run(d, sol, cost, 35, 0.05, 0.97, 3, True, 3, 9, dev, chain_base=40)
+    b = sa_subset_run(d, a[3], a[4], 55, 0.05, 0.97, 3, True, 3, 9, dev, it_begin=35, temp_start=a[5], best=a[0],
+                      best_cost=a[1], chain_base=40)
+    total = {k: a[2][k] + b[2][k] for k in a[2]}
+    _state_equal(want, (b[0], b[1], total, b[3], b[4], b[5]))
+
+
+@pytest.mark.gpu
+def test_simulated_annealing_gpu_equals_cpu(cuda):
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    data = _random(517, 12, 3)
+    kw = dict(n_chains=40, iters=80, t0=0.05, cooling=0.97, interval=3, seed=9, locally_optimize=False)
+    rc = SimulatedAnnealing(_domain(data, min_size=2, max_size=8), use_kernel=True, **kw).run()
+    rg = SimulatedAnnealing(_domain(data, device="cuda", min_size=2, max_size=8), **kw).run()
+    assert rg.stats["engine"] == "sa_subset_kernel" and rc.stats["engine"] == "sa_subset_host"     # the GPU default
+    assert rg.best_cost == rc.best_cost and torch.equal(rg.best.cpu(), rc.best)
+    assert torch.equal(rg.costs.cpu(), rc.costs) and torch.equal(rg.solutions.cpu(), rc.solutions)
+    assert {k: v for k, v in rg.stats.items() if k != "engine"} == {k: v for k, v in rc.stats.items() if k != "engine"}
+
+
+@pytest.mark.gpu
+def test_row_cap_of_the_default_dispatch(cuda):
+    """Above ga_subset.SA_ROW_CAP rows the default stays on the generic path; use_kernel=True still
+    forces the engine."""
+    from avenir_amd.optimize import ga_subset
+    from avenir_amd.optimize.search import SimulatedAnnealing
+    for n, expect in ((ga_subset.SA_ROW_CAP, True), (ga_subset.SA_ROW_CAP + 1, False)):
+        d = _domain(_random(n, 2, 2), device="cuda")
+        assert (SimulatedAnnealing(d)._chain_engine() is not None) == expect
+        assert SimulatedAnnealing(d, use_kernel=True)._chain_engine() is not None
+        assert SimulatedAnnealing(d, use_kernel=False)._chain_engine() is None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["mask_value_2", "max_retry", "F_mismatch"])
+def test_binding_validation(cuda, case):
+    """Each violation raises before anything is launched: every tensor stays as it was."""
+    from avenir_amd import _native
+    from avenir_amd.optimize.ga_subset import _device_tables
+    _, tb = _tables("reference")
+    dev = torch.device("cuda")
+    sol, cost = _start(tb, 6, 1, 0)
+    max_retry = -1 if case == "max_retry" else 3
+    if case == "mask_value_2":
+        sol = sol.copy()
+        sol[4, 3] = 2
+    if case == "F_mismatch":
+        sol = np.zeros((6, 13), dtype=np.int16)
+    ts, tc = torch.from_numpy(sol).to(dev), torch.from_numpy(cost).to(dev)
+    tb_, tbc = ts.clone(), tc.clone()
+    st = torch.zeros(4, dtype=torch.long, device=dev)
+    keep = ts.clone(), tc.clone()
+    with pytest.raises((RuntimeError, ValueError)):
+        _native.C().sa_subset(*_device_tables(tb, dev), 2, 8, ts, tc, tb_, tbc, 5, 0.05, 0.97, 3, True, max_retry, 1, 0,
+                              st, 0, 0.05, 0, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(ts, keep[0]) and torch.equal(tc, keep[1]) and torch.equal(tb_, keep[0])
+    assert torch.equal(tbc, keep[1]) and bool((st == 0).all())
