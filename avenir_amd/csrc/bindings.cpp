@@ -1381,47 +1381,6 @@ at::Tensor sample(int64_t dist, int64_t n, const at::Tensor& params, const c10::
 // ---------------------------------------------------------------------------------------------
 // optimisation (K22)
 // ---------------------------------------------------------------------------------------------
-void sa_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, bool swap, at::Tensor& sol,
-               at::Tensor& cur_cost, at::Tensor& best_sol, at::Tensor& best_cost, int64_t iters, double t0,
-               double cool, int64_t interval, bool geometric, int64_t max_retry, int64_t seed, int64_t offset,
-               at::Tensor& stats, int64_t it_begin, double temp_start, int64_t chain_base) {
-  CHECK_DEV(cost);
-  CHECK_DTYPE(cost, at::kFloat);
-  TORCH_CHECK(cost.dim() == 2 && cost.size(1) >= 2, "cost must be [L, V>=2]");
-  const int64_t L = cost.size(0), V = cost.size(1);
-  TORCH_CHECK(V <= 32767 && L <= 512, "V or L too large (L <= 512: the [L][64] solution tile lives in LDS)");
-  CHECK_DEV(sol);
-  CHECK_DTYPE(sol, at::kShort);
-  TORCH_CHECK(sol.dim() == 2 && sol.size(1) == L, "sol must be [P, L]");
-  const int64_t P = sol.size(0);
-  TORCH_CHECK(sol.min().item<int>() >= 0 && sol.max().item<int>() < V, "solution values out of range");
-  CHECK_DEV(best_sol);
-  CHECK_DTYPE(best_sol, at::kShort);
-  TORCH_CHECK(best_sol.sizes() == sol.sizes(), "best_sol shape");
-  for (at::Tensor* t : {&cur_cost, &best_cost}) {
-    CHECK_DEV((*t));
-    CHECK_DTYPE((*t), at::kFloat);
-    TORCH_CHECK(t->numel() == P, "cost vectors must be [P]");
-  }
-  CHECK_DEV(stats);
-  CHECK_DTYPE(stats, at::kLong);
-  TORCH_CHECK(stats.numel() >= 4, "stats needs 4 entries (3 counters + hand-off temperature)");
-  const uint8_t* cf = nullptr;
-  if (conflict.has_value() && conflict->defined()) {
-    CHECK_DEV((*conflict));
-    CHECK_DTYPE((*conflict), at::kByte);
-    TORCH_CHECK(conflict->dim() == 2 && conflict->size(0) == L && conflict->size(1) == L, "conflict [L, L]");
-    cf = conflict->data_ptr<uint8_t>();
-  }
-  DevGuard g(cost.device());
-  avk::sa_assign(cost.data_ptr<float>(), (int)L, (int)V, cf, swap ? 1 : 0, sol.data_ptr<int16_t>(), cur_cost.data_ptr<float>(),
-                 best_sol.data_ptr<int16_t>(), best_cost.data_ptr<float>(), (int)P, (int)iters, (float)t0,
-                 (float)cool, (int)interval, geometric ? 1 : 0, (int)max_retry, (unsigned long long)seed,
-                 (unsigned long long)offset, (int)it_begin, (float)temp_start,
-                 reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), (long long)chain_base,
-                 cur_stream(cost));
-}
-
 // The checks shared by the island GA bindings (optim.hip): pop int16 [islands, P, L] with its costs
 // and hist [islands, G] on one device, the kernels' pool limits and the generation counters.
 // Returns (islands, P).
@@ -1635,8 +1594,8 @@ void ga_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tens
                  (unsigned long long)seed, (long long)island_base, (unsigned long long)gen_base, cur_stream(LL));
 }
 
-// The checks shared by the SA chain bindings (optim.hip::sa_meeting_kernel, sa_subset_kernel): the
-// resumable state on one device and Philox counters that stay inside 64 bits.  Returns the chain
+// The checks shared by the SA chain bindings (optim.hip::sa_assign_kernel, sa_meeting_kernel,
+// sa_subset_kernel): the resumable state on one device and Philox counters that stay inside 64 bits.  Returns the chain
 // count and the run.
 static std::pair<int64_t, avk::SaRun> sa_check(const char* who, int64_t L, const at::Tensor& sol,
                                                const at::Tensor& cur_cost, const at::Tensor& best_sol,
@@ -1671,6 +1630,34 @@ static std::pair<int64_t, avk::SaRun> sa_check(const char* who, int64_t L, const
   return {P, avk::SaRun{(long long)iters, (long long)it_begin, (float)t0, (float)cool, (long long)interval,
                         geometric ? 1 : 0, (int)max_retry, (unsigned long long)seed, (unsigned long long)offset,
                         (float)temp_start, (long long)chain_base}};
+}
+
+void sa_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, bool swap, at::Tensor& sol,
+               at::Tensor& cur_cost, at::Tensor& best_sol, at::Tensor& best_cost, int64_t iters, double t0,
+               double cool, int64_t interval, bool geometric, int64_t max_retry, int64_t seed, int64_t offset,
+               at::Tensor& stats, int64_t it_begin, double temp_start, int64_t chain_base) {
+  CHECK_DEV(cost);
+  CHECK_DTYPE(cost, at::kFloat);
+  TORCH_CHECK(cost.dim() == 2 && cost.size(1) >= 2 && cost.is_contiguous(), "cost must be contiguous [L, V>=2]");
+  const int64_t L = cost.size(0), V = cost.size(1);
+  TORCH_CHECK(V <= 32767 && L <= 512, "V or L too large (L <= 512: the [L][64] solution tile lives in LDS)");
+  const auto [P, run] = sa_check("sa_assign", L, sol, cur_cost, best_sol, best_cost, stats, iters, t0, cool, interval,
+                                 geometric, max_retry, seed, offset, it_begin, temp_start, chain_base);
+  TORCH_CHECK(sol.device() == cost.device(), "sa_assign: tensors on one device");
+  if (sol.numel())
+    TORCH_CHECK(sol.min().item<int>() >= 0 && sol.max().item<int>() < V, "solution values out of range");
+  const uint8_t* cf = nullptr;
+  if (conflict.has_value() && conflict->defined()) {
+    CHECK_DEV((*conflict));
+    CHECK_DTYPE((*conflict), at::kByte);
+    TORCH_CHECK(conflict->dim() == 2 && conflict->size(0) == L && conflict->size(1) == L && conflict->is_contiguous() &&
+                    conflict->device() == cost.device(), "conflict must be contiguous [L, L] on the device of cost");
+    cf = conflict->data_ptr<uint8_t>();
+  }
+  DevGuard g(cost.device());
+  avk::sa_assign(cost.data_ptr<float>(), (int)L, (int)V, cf, swap ? 1 : 0, sol.data_ptr<int16_t>(),
+                 cur_cost.data_ptr<float>(), best_sol.data_ptr<int16_t>(), best_cost.data_ptr<float>(), (int)P, run,
+                 reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), cur_stream(cost));
 }
 
 void sa_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,

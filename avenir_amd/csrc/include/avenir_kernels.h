@@ -153,13 +153,8 @@ void ga_subset(const float* LL, const float* log_prior, const int* labels, int N
                int max_size, float invalid, short* pop, float* pop_cost, float* hist, int islands, int P, int G, int m,
                int r, int purge_first, int mutate, unsigned long long seed, long long island_base,
                unsigned long long gen_base, hipStream_t stream);
-void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
-               short* best_sol, float* best_cost, int P, int iters, float t0, float cool, int interval,
-               int geometric, int max_retry, unsigned long long seed, unsigned long long offset,
-               int it_begin, float temp_start, unsigned long long* stats, long long chain_base,
-               hipStream_t stream);
-// SA chains over the meeting-schedule and feature-subset domains (one launch, resumable like
-// sa_assign): sol / best_sol int16 [P][L], cur_cost / best_cost [P] in and out, stats[4] = better,
+// SA chains over assignment, meeting-schedule and feature-subset domains (one launch, resumable):
+// sol / best_sol int16 [P][L], cur_cost / best_cost [P] in and out, stats[4] = better,
 // worse_accepted, rejected (added) and the hand-off temperature's bits.  Row p is global chain
 // chain_base + p; moves [it_begin, it_begin + iters) with 64-bit Philox counters throughout.
 struct SaRun {
@@ -171,6 +166,10 @@ struct SaRun {
   float temp_start;
   long long chain_base;
 };
+// cost [L][V], conflict [L][L] or null; 1 <= L <= 512 (the [L][64] solution tile lives in LDS)
+void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
+               short* best_sol, float* best_cost, int P, const SaRun& run, unsigned long long* stats,
+               hipStream_t stream);
 size_t sa_meeting_lds(int M);
 void sa_meeting(const GaMeetingDomain& dom, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P,
                 const SaRun& run, unsigned long long* stats, hipStream_t stream);

@@ -1,13 +1,14 @@
-// K22: many simulated-annealing chains in one persistent launch (CDNA4, gfx950).
+// K22: stochastic search in persistent launches (CDNA4, gfx950) — island genetic algorithms and
+// simulated-annealing chains over three domains each: assignments (a [L][V] cost table and an
+// [L][L] conflict table), meeting schedules and feature subsets scored by naive Bayes.
 //
-// Reference: one SA chain per Spark partition, mutating string-encoded solutions through the
-// BasicSearchDomain SPI (S/optimize/SimulatedAnnealing.scala:111-187,
-// J/optimize/BasicSearchDomain.java:272-394, cost J/examples/TaskScheduleSearch.java:169-305).
-// Here an assignment-type domain (solution s[L] with s[i] in [0, V); total cost = mean_i C[i][s[i]];
-// a solution is invalid when two positions with a conflict share a value) is compiled into a
-// [L][V] cost table and an [L][L] conflict table, and every lane runs one chain for `iters`
-// Metropolis steps: O(1) cost delta per move, O(L) validity check, Philox randomness, geometric or
-// linear cooling — the whole optimisation is one kernel launch for thousands of chains.
+// Reference: one SA chain or one GA per Spark partition, mutating string-encoded solutions through
+// the BasicSearchDomain SPI (S/optimize/SimulatedAnnealing.scala:111-187,
+// S/optimize/GeneticAlgorithm.scala:70-163, J/optimize/BasicSearchDomain.java:272-394, cost
+// J/examples/TaskScheduleSearch.java:169-305).  Here a whole optimisation is one launch: an island
+// is a workgroup (ga_assign_kernel, ga_meeting_kernel, ga_subset_kernel on one frame, ga_island),
+// and an SA chain is a lane (sa_assign_kernel, sa_meeting_kernel) or 1 to 16 waves
+// (sa_subset_kernel), thousands of chains per launch, all launched from one run record (SaRun).
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -16,99 +17,6 @@
 #include "avenir_kernels.h"
 
 namespace {
-
-// true when position i conflicts with no other position holding the same value
-__device__ __forceinline__ bool position_ok(const short* s, int L, int i, const uint8_t* __restrict__ conflict) {
-  const short v = s[i * 64];
-  const uint8_t* row = conflict + (long long)i * L;
-  for (int j = 0; j < L; ++j)
-    if (j != i && s[j * 64] == v && row[j]) return false;
-  return true;
-}
-
-// One chain per lane, 64-lane workgroups (one wave): the chain's current solution lives in LDS as
-// column `lane` of an [L][64] short tile (lane-private, conflict-free), the best solution is written
-// to global memory only on improvement.  Move = reassign one position to a different value; with
-// `swap` set, the position that already held the new value takes the old one (the reference's
-// replaceSolutionComponent, J/examples/TaskScheduleSearch.java:140-166).
-__global__ __launch_bounds__(64) void sa_assign_kernel(
-    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, int swap,
-    short* __restrict__ sol, float* __restrict__ cur_cost, short* __restrict__ best_sol,
-    float* __restrict__ best_cost, int P, int iters, float t0, float cool, int interval, int geometric,
-    int max_retry, unsigned long long seed, unsigned long long offset, int it_begin, float temp_start,
-    unsigned long long* __restrict__ stats, long long chain_base) {
-  extern __shared__ short lds_sol[];
-  const int lane = threadIdx.x;
-  const int p = blockIdx.x * 64 + lane;
-  const bool live = p < P;
-  // Philox stream of GLOBAL chain chain_base + p: a chain draws the same moves whichever rank
-  // (and launch) runs it, so chains can be re-dealt over a different world size on resume
-  const unsigned long long gp = (unsigned long long)(chain_base + p);
-  short* s = lds_sol + lane;  // element j at s[j * 64]
-  if (live)
-    for (int j = 0; j < L; ++j) s[j * 64] = sol[(long long)p * L + j];
-  if (!live) return;
-  short* bs = best_sol + (long long)p * L;
-  float c = cur_cost[p];
-  float bc = best_cost[p];
-  // resumable: a run split into segments [it_begin, it_begin + iters) draws the same Philox counters
-  // and follows the same cooling schedule as one uninterrupted launch
-  float temp = temp_start;
-  unsigned long long acc_better = 0, acc_worse = 0, rejected = 0;
-  const float invL = 1.f / (float)L;
-  for (int it = it_begin; it < it_begin + iters; ++it) {
-    int pos = -1, nv = 0, old = 0, j2 = -1;
-    for (int tr = 0; tr <= max_retry; ++tr) {
-      const av::u4 r = av::philox_draw(seed, offset + (unsigned long long)it * (max_retry + 1) + tr, gp);
-      const int cp = min((int)(av::u32_to_unit(r.x) * (float)L), L - 1);
-      int cv = min((int)(av::u32_to_unit(r.y) * (float)(V - 1)), V - 2);
-      const int ov = s[cp * 64];
-      if (cv >= ov) ++cv;  // a different value
-      int sw = -1;
-      if (swap)
-        for (int j = 0; j < L; ++j)
-          if (j != cp && s[j * 64] == cv) { sw = j; break; }
-      s[cp * 64] = (short)cv;
-      if (sw >= 0) s[sw * 64] = (short)ov;
-      const bool ok = !conflict || (position_ok(s, L, cp, conflict) && (sw < 0 || position_ok(s, L, sw, conflict)));
-      if (ok) { pos = cp; nv = cv; old = ov; j2 = sw; break; }
-      s[cp * 64] = (short)ov;
-      if (sw >= 0) s[sw * 64] = (short)cv;
-    }
-    if (pos >= 0) {
-      float delta = cost[(long long)pos * V + nv] - cost[(long long)pos * V + old];
-      if (j2 >= 0) delta += cost[(long long)j2 * V + old] - cost[(long long)j2 * V + nv];
-      delta *= invL;
-      const av::u4 r2 = av::philox_draw(seed ^ 0x9e3779b97f4a7c15ull, offset + it, gp);
-      const bool accept = delta <= 0.f || av::u32_to_unit(r2.x) < __expf(-delta / fmaxf(temp, 1e-12f));
-      if (accept) {
-        c += delta;
-        if (delta <= 0.f) ++acc_better; else ++acc_worse;
-        if (c < bc) {
-          bc = c;
-          for (int j = 0; j < L; ++j) bs[j] = s[j * 64];
-        }
-      } else {
-        s[pos * 64] = (short)old;
-        if (j2 >= 0) s[j2 * 64] = (short)nv;
-        ++rejected;
-      }
-    }
-    // cooling every `interval` moves: geometric, or linear T0 - it * rate (the Python optimiser's
-    // form, P/mlextra/optsolo.py:84-88; the Scala linear branch subtracts T0 each time, a bug)
-    if (interval > 0 && (it + 1) % interval == 0)
-      temp = geometric ? temp * cool : fmaxf(t0 - (float)(it + 1) * cool, 1e-12f);
-  }
-  for (int j = 0; j < L; ++j) sol[(long long)p * L + j] = s[j * 64];
-  cur_cost[p] = c;
-  best_cost[p] = bc;
-  if (stats) {
-    if (p == 0) stats[3] = (unsigned long long)__float_as_uint(temp);  // segment hand-off temperature
-    atomicAdd(&stats[0], acc_better);
-    atomicAdd(&stats[1], acc_worse);
-    atomicAdd(&stats[2], rejected);
-  }
-}
 
 // ---- island genetic algorithm: one workgroup per island, G generations per launch ---------------
 // Reference: Spark GA — an independent GA per partition (S/optimize/GeneticAlgorithm.scala:70-163) —
@@ -792,7 +700,7 @@ __global__ __launch_bounds__(1024) void ga_subset_kernel(
   });
 }
 
-// ---- simulated-annealing chains over the meeting-schedule and feature-subset domains ------------
+// ---- simulated-annealing chains over assignment, meeting-schedule and feature-subset domains ----
 // Reference: the Spark simulatedAnnealing job and SimulatedAnnealingOptimizer
 // (P/mlextra/optsolo.py:34-88, which `fesel sa` drives).  Chain g = chain_base + p is GLOBAL; move
 // `it` of [it_begin, it_begin + iters):
@@ -809,7 +717,7 @@ __global__ __launch_bounds__(1024) void ga_subset_kernel(
 // Every fp32 operation is rounded on its own (no contraction) and sa_exp is built from such
 // operations alone, so optimize/sa.py::sa_chains_reference equals the kernels bit for bit, the
 // Metropolis decision included.  What a solution is, when it is valid and what it costs is the
-// domain's: each kernel supplies propose / price / settle / improved to sa_chain.
+// domain's: the meeting and subset kernels supply propose / price / settle / improved to sa_chain.
 struct SaArgs {
   int P;
   long long iters, it_begin;
@@ -908,6 +816,104 @@ __device__ __forceinline__ void sa_report(unsigned long long* __restrict__ stats
   if (S.better) atomicAdd(&stats[0], S.better);
   if (S.worse) atomicAdd(&stats[1], S.worse);
   if (S.rejected) atomicAdd(&stats[2], S.rejected);
+}
+
+// true when position i conflicts with no other position holding the same value
+__device__ __forceinline__ bool position_ok(const short* s, int L, int i, const uint8_t* __restrict__ conflict) {
+  const short v = s[i * 64];
+  const uint8_t* row = conflict + (long long)i * L;
+  for (int j = 0; j < L; ++j)
+    if (j != i && s[j * 64] == v && row[j]) return false;
+  return true;
+}
+
+// Assignments (s[i] in [0, V); cost = mean_i C[i][s[i]]; invalid when two positions with a conflict
+// share a value).  The kernel keeps its own arguments, 32-bit move counter and stats hand-off: its
+// loop is latency-bound with the scalar registers at their cap and ran 1.7 to 7 % slower on SaArgs /
+// SaChain.  It prices by the O(1) cost delta, accepts through __expf and cools by an expression the
+// compiler may contract: optimize/sa.py::sa_assign_reference follows it closely, not bit for bit.
+// One chain per lane, 64-lane workgroups (one wave): the chain's current solution lives in LDS as
+// column `lane` of an [L][64] short tile (lane-private, conflict-free), the best solution is written
+// to global memory only on improvement.  Move = reassign one position to a different value; with
+// `swap` set, the position that already held the new value takes the old one (the reference's
+// replaceSolutionComponent, J/examples/TaskScheduleSearch.java:140-166).
+__global__ __launch_bounds__(64) void sa_assign_kernel(
+    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, int swap,
+    short* __restrict__ sol, float* __restrict__ cur_cost, short* __restrict__ best_sol,
+    float* __restrict__ best_cost, int P, int iters, float t0, float cool, int interval, int geometric,
+    int max_retry, unsigned long long seed, unsigned long long offset, int it_begin, float temp_start,
+    unsigned long long* __restrict__ stats, long long chain_base) {
+  extern __shared__ short lds_sol[];
+  const int lane = threadIdx.x;
+  const int p = blockIdx.x * 64 + lane;
+  const bool live = p < P;
+  // Philox stream of GLOBAL chain chain_base + p: a chain draws the same moves whichever rank
+  // (and launch) runs it, so chains can be re-dealt over a different world size on resume
+  const unsigned long long gp = (unsigned long long)(chain_base + p);
+  short* s = lds_sol + lane;  // element j at s[j * 64]
+  if (live)
+    for (int j = 0; j < L; ++j) s[j * 64] = sol[(long long)p * L + j];
+  if (!live) return;
+  short* bs = best_sol + (long long)p * L;
+  float c = cur_cost[p];
+  float bc = best_cost[p];
+  // resumable: a run split into segments [it_begin, it_begin + iters) draws the same Philox counters
+  // and follows the same cooling schedule as one uninterrupted launch
+  float temp = temp_start;
+  unsigned long long acc_better = 0, acc_worse = 0, rejected = 0;
+  const float invL = 1.f / (float)L;
+  for (int it = it_begin; it < it_begin + iters; ++it) {
+    int pos = -1, nv = 0, old = 0, j2 = -1;
+    for (int tr = 0; tr <= max_retry; ++tr) {
+      const av::u4 r = av::philox_draw(seed, offset + (unsigned long long)it * (max_retry + 1) + tr, gp);
+      const int cp = min((int)(av::u32_to_unit(r.x) * (float)L), L - 1);
+      int cv = min((int)(av::u32_to_unit(r.y) * (float)(V - 1)), V - 2);
+      const int ov = s[cp * 64];
+      if (cv >= ov) ++cv;  // a different value
+      int sw = -1;
+      if (swap)
+        for (int j = 0; j < L; ++j)
+          if (j != cp && s[j * 64] == cv) { sw = j; break; }
+      s[cp * 64] = (short)cv;
+      if (sw >= 0) s[sw * 64] = (short)ov;
+      const bool ok = !conflict || (position_ok(s, L, cp, conflict) && (sw < 0 || position_ok(s, L, sw, conflict)));
+      if (ok) { pos = cp; nv = cv; old = ov; j2 = sw; break; }
+      s[cp * 64] = (short)ov;
+      if (sw >= 0) s[sw * 64] = (short)cv;
+    }
+    if (pos >= 0) {
+      float delta = cost[(long long)pos * V + nv] - cost[(long long)pos * V + old];
+      if (j2 >= 0) delta += cost[(long long)j2 * V + old] - cost[(long long)j2 * V + nv];
+      delta *= invL;
+      const av::u4 r2 = av::philox_draw(seed ^ 0x9e3779b97f4a7c15ull, offset + it, gp);
+      const bool accept = delta <= 0.f || av::u32_to_unit(r2.x) < __expf(-delta / fmaxf(temp, 1e-12f));
+      if (accept) {
+        c += delta;
+        if (delta <= 0.f) ++acc_better; else ++acc_worse;
+        if (c < bc) {
+          bc = c;
+          for (int j = 0; j < L; ++j) bs[j] = s[j * 64];
+        }
+      } else {
+        s[pos * 64] = (short)old;
+        if (j2 >= 0) s[j2 * 64] = (short)nv;
+        ++rejected;
+      }
+    }
+    // cooling every `interval` moves: geometric, or linear T0 - it * rate (the Python optimiser's
+    // form, P/mlextra/optsolo.py:84-88; the Scala linear branch subtracts T0 each time, a bug)
+    if (interval > 0 && (it + 1) % interval == 0)
+      temp = geometric ? temp * cool : fmaxf(t0 - (float)(it + 1) * cool, 1e-12f);
+  }
+  for (int j = 0; j < L; ++j) sol[(long long)p * L + j] = s[j * 64];
+  cur_cost[p] = c;
+  best_cost[p] = bc;
+  if (stats) {
+    if (p == 0) stats[3] = (unsigned long long)__float_as_uint(temp);  // segment hand-off temperature
+    atomicAdd(&stats[0], acc_better);
+    atomicAdd(&stats[1], acc_worse);
+    atomicAdd(&stats[2], rejected);
+  }
 }
 
 // Meeting schedules: one chain per lane, 64-lane workgroups.  The chain's index triples, start
@@ -1100,15 +1106,20 @@ size_t ga_meeting_lds(int P, int L, int r) {
          ga_a16((size_t)MT_DOM_INTS * sizeof(int));
 }
 
+// the limits of the meeting-schedule kernels (what mt_stage keeps in LDS)
+static void mt_check(const char* who, const GaMeetingDomain& dom) {
+  if (dom.M < 1 || dom.M > MT_MAX_M || dom.Q < 1 || dom.Q > MT_MAX_Q)
+    throw std::invalid_argument(std::string(who) + ": 1 <= M <= 32, 1 <= Q <= 256");
+  if (dom.nd < 1 || dom.nd > MT_MAX_CARD || dom.nh < 1 || dom.nh > MT_MAX_CARD || dom.nm < 1 || dom.nm > MT_MAX_CARD)
+    throw std::invalid_argument(std::string(who) + ": value tables of 1..32 entries");
+  if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
+    throw std::invalid_argument(std::string(who) + ": at most 16 blocked entries and 16 ordered pairs");
+}
+
 void ga_meeting(const GaMeetingDomain& dom, float invalid, short* pop, float* pop_cost, float* hist, int islands,
                 int P, int G, int m, int r, int purge_first, int mutate, unsigned long long seed,
                 long long island_base, unsigned long long gen_base, hipStream_t stream) {
-  if (dom.M < 1 || dom.M > MT_MAX_M || dom.Q < 1 || dom.Q > MT_MAX_Q)
-    throw std::invalid_argument("ga_meeting: 1 <= M <= 32, 1 <= Q <= 256");
-  if (dom.nd < 1 || dom.nd > MT_MAX_CARD || dom.nh < 1 || dom.nh > MT_MAX_CARD || dom.nm < 1 || dom.nm > MT_MAX_CARD)
-    throw std::invalid_argument("ga_meeting: value tables of 1..32 entries");
-  if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
-    throw std::invalid_argument("ga_meeting: at most 16 blocked entries and 16 ordered pairs");
+  mt_check("ga_meeting", dom);
   ga_check_pool("ga_meeting", P, m, r, purge_first);
   const size_t lds = ga_meeting_lds(P, 3 * dom.M, r);
   if (lds > 64 * 1024) throw std::invalid_argument("ga_meeting: pool, children and costs exceed 64 KiB of LDS");
@@ -1161,18 +1172,6 @@ void ga_subset(const float* LL, const float* log_prior, const int* labels, int N
   AV_HIP_CHECK(hipGetLastError());
 }
 
-void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
-               short* best_sol, float* best_cost, int P, int iters, float t0, float cool, int interval,
-               int geometric, int max_retry, unsigned long long seed, unsigned long long offset,
-               int it_begin, float temp_start, unsigned long long* stats, long long chain_base, hipStream_t stream) {
-  if (P <= 0 || iters <= 0) return;
-  const size_t lds = (size_t)L * 64 * sizeof(short);
-  sa_assign_kernel<<<(P + 63) / 64, 64, lds, stream>>>(cost, L, V, conflict, swap, sol, cur_cost, best_sol,
-                                                       best_cost, P, iters, t0, cool, interval, geometric, max_retry,
-                                                       seed, offset, it_begin, temp_start, stats, chain_base);
-  AV_HIP_CHECK(hipGetLastError());
-}
-
 static SaArgs sa_args(const char* who, const SaRun& r, int P) {
   if (r.iters < 0 || r.it_begin < 0 || r.max_retry < 0 || r.max_retry >= (1 << 20) ||
       r.it_begin + r.iters >= (1LL << 40))
@@ -1181,18 +1180,29 @@ static SaArgs sa_args(const char* who, const SaRun& r, int P) {
                 r.temp_start, r.chain_base};
 }
 
+void sa_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* sol, float* cur_cost,
+               short* best_sol, float* best_cost, int P, const SaRun& run, unsigned long long* stats,
+               hipStream_t stream) {
+  if (L < 1 || L > 512 || V < 2 || V > 32767)
+    throw std::invalid_argument("sa_assign: 1 <= L <= 512 (the [L][64] solution tile is 64 KiB of LDS), 2 <= V <= 32767");
+  const SaArgs A = sa_args("sa_assign", run, P);
+  if (A.it_begin + A.iters >= (1LL << 31) || A.interval != (int)A.interval)
+    throw std::invalid_argument("sa_assign: it_begin + iters and interval must fit 31 bits (the kernel's move counter)");
+  if (P <= 0 || run.iters <= 0) return;
+  const size_t lds = (size_t)L * 64 * sizeof(short);
+  sa_assign_kernel<<<(P + 63) / 64, 64, lds, stream>>>(
+      cost, L, V, conflict, swap, sol, cur_cost, best_sol, best_cost, P, (int)A.iters, A.t0, A.cool, (int)A.interval,
+      A.geometric, A.max_retry, A.seed, A.offset, (int)A.it_begin, A.temp_start, stats, A.chain_base);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
 size_t sa_meeting_lds(int M) {
   return (size_t)3 * M * 64 * sizeof(short) + (size_t)2 * M * 64 * sizeof(int) + (size_t)MT_DOM_INTS * sizeof(int);
 }
 
 void sa_meeting(const GaMeetingDomain& dom, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P,
                 const SaRun& run, unsigned long long* stats, hipStream_t stream) {
-  if (dom.M < 1 || dom.M > MT_MAX_M || dom.Q < 1 || dom.Q > MT_MAX_Q)
-    throw std::invalid_argument("sa_meeting: 1 <= M <= 32, 1 <= Q <= 256");
-  if (dom.nd < 1 || dom.nd > MT_MAX_CARD || dom.nh < 1 || dom.nh > MT_MAX_CARD || dom.nm < 1 || dom.nm > MT_MAX_CARD)
-    throw std::invalid_argument("sa_meeting: value tables of 1..32 entries");
-  if (dom.nb < 0 || dom.nb > MT_MAX_LIST || dom.no < 0 || dom.no > MT_MAX_LIST)
-    throw std::invalid_argument("sa_meeting: at most 16 blocked entries and 16 ordered pairs");
+  mt_check("sa_meeting", dom);
   const SaArgs A = sa_args("sa_meeting", run, P);
   const size_t lds = sa_meeting_lds(dom.M);
   if (lds > 64 * 1024) throw std::invalid_argument("sa_meeting: the chains' tiles exceed 64 KiB of LDS");

@@ -4,7 +4,7 @@ from .domain import AssignmentDomain, CallbackDomain, FunctionDomain, SearchDoma
 from .domains import FeatureSubsetDomain, MeetingScheduleDomain, TaskScheduleSearch, geo_distance, read_lenient_json
 from .ga_meeting import sa_meeting_reference, sa_meeting_run
 from .ga_subset import sa_subset_reference, sa_subset_run
-from .sa import SaDomain, sa_chains_init, sa_chains_reference, sa_exp
+from .sa import SaDomain, SaRun, sa_chains_init, sa_chains_reference, sa_exp
 from .search import (BayesianOptimizer, EvolutionaryOptimizer, GeneticAlgorithm, OptResult, RandomSearch,
                      SimulatedAnnealing, TabuSearch, local_focussed, local_trajectory, parameter_search, sa_assign,
                      sa_assign_reference)
@@ -14,6 +14,6 @@ __all__ = [
     "MeetingScheduleDomain", "TaskScheduleSearch", "geo_distance", "read_lenient_json", "BayesianOptimizer",
     "EvolutionaryOptimizer", "GeneticAlgorithm", "OptResult", "RandomSearch", "SimulatedAnnealing", "TabuSearch",
     "local_focussed", "local_trajectory", "parameter_search", "sa_assign", "sa_assign_reference",
-    "SaDomain", "sa_chains_init", "sa_chains_reference", "sa_exp", "sa_meeting_reference", "sa_meeting_run",
+    "SaDomain", "SaRun", "sa_chains_init", "sa_chains_reference", "sa_exp", "sa_meeting_reference", "sa_meeting_run",
     "sa_subset_reference", "sa_subset_run",
 ]

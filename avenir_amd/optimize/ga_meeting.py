@@ -23,6 +23,7 @@ import torch
 from ..ops.random import u32_to_unit
 from .ga import (GaDomain, _set, _unit_index, ga_assign_lds, ga_islands_launch, ga_islands_reference, ga_redraw_init,
                  splice)
+from .sa import SaDomain, SaRun, sa_chains_init, sa_chains_launch, sa_chains_twin
 
 MAX_M, MAX_Q, MAX_CARD, MAX_LIST = 32, 256, 32, 16      # the kernel's limits
 _TIME_LIMIT = 1 << 24                                     # seconds: exact in int32 and in fp32
@@ -225,23 +226,30 @@ def sa_meeting_lds(M: int) -> int:
 
 def sa_meeting_init(tables: dict, n: int, seed: int, chain_base: int) -> np.ndarray:
     """Start schedules [n, 3 M] int16 of global chains ``chain_base ..`` (:func:`~avenir_amd.optimize.sa.sa_chains_init`)."""
-    from .sa import sa_chains_init
     return sa_chains_init(tables["cards"], lambda s: ga_meeting_valid(tables, s), n, seed, chain_base)
+
+
+def sa_meeting_advance(tables: dict, sol, cost, run: SaRun, device, best=None, best_cost=None):
+    """One segment: ``sa_meeting_kernel`` on a GPU, on the host its twin — the chain frame of
+    :mod:`~avenir_amd.optimize.sa` with the island kernel's mutation as the proposal, ``mt_valid`` and
+    ``mt_cost``.  Returns (best int16, best_cost, stats, sol int16, cost, temperature)."""
+    if torch.device(device).type == "cuda":
+        from .. import _native
+        return sa_chains_launch(_native.C().sa_meeting, tuple(_device_tables(tables, device)), (), sol, cost, run, best,
+                                best_cost, device)
+    dom = SaDomain(propose=lambda s, x, y: _mutated(tables, s, x, y), valid=lambda s: ga_meeting_valid(tables, s),
+                   price=lambda s: ga_meeting_price(tables, s))
+    b, bc, st, s, c, temp = sa_chains_twin(dom, np.array(sol, dtype=np.int64), cost, run,
+                                           None if best is None else np.array(best, dtype=np.int64), best_cost)
+    return b.astype(np.int16), bc, st, s.astype(np.int16), c, temp
 
 
 def sa_meeting_reference(tables: dict, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float,
                          interval: int, geometric: bool, max_retry: int, seed: int, offset: int = 0, it_begin: int = 0,
                          temp_start=None, best=None, best_cost=None, chain_base: int = 0):
-    """Host twin of ``sa_meeting_kernel``: the chain frame of :mod:`~avenir_amd.optimize.sa` with the
-    island kernel's mutation as the proposal, ``mt_valid`` and ``mt_cost``.  Returns (best int16,
-    best_cost, stats, sol int16, cost, temperature)."""
-    from .sa import SaDomain, sa_chains_reference
-    dom = SaDomain(propose=lambda s, x, y: _mutated(tables, s, x, y), valid=lambda s: ga_meeting_valid(tables, s),
-                   price=lambda s: ga_meeting_price(tables, s))
-    b, bc, st, s, c, temp = sa_chains_reference(
-        dom, np.array(sol, dtype=np.int64), cost, iters, t0, cool, interval, geometric, max_retry, seed, offset,
-        it_begin, temp_start, None if best is None else np.array(best, dtype=np.int64), best_cost, chain_base)
-    return b.astype(np.int16), bc, st, s.astype(np.int16), c, temp
+    """Host twin of ``sa_meeting_kernel`` (:func:`sa_meeting_advance` on the host)."""
+    return sa_meeting_advance(tables, sol, cost, SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset,
+                                                       it_begin, temp_start, chain_base), "cpu", best, best_cost)
 
 
 def sa_meeting_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float, interval: int,
@@ -253,12 +261,5 @@ def sa_meeting_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: fl
     tables = domain if isinstance(domain, dict) else meeting_tables(domain)
     if tables is None:
         raise ValueError("the domain is outside the meeting kernel's limits")
-    device = torch.device(device)
-    if device.type == "cuda":
-        from .. import _native
-        from .sa import sa_chains_launch
-        return sa_chains_launch(_native.C().sa_meeting, tuple(_device_tables(tables, device)), (), sol, cost, iters, t0,
-                                cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, best,
-                                best_cost, chain_base, device)
-    return sa_meeting_reference(tables, sol, cost, iters, t0, cool, interval, geometric, max_retry, seed, offset,
-                                it_begin, temp_start, best, best_cost, chain_base)
+    return sa_meeting_advance(tables, sol, cost, SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset,
+                                                       it_begin, temp_start, chain_base), device, best, best_cost)

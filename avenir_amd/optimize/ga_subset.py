@@ -28,6 +28,7 @@ import torch
 
 from ..ops.random import u32_to_unit
 from .ga import GaDomain, _unit_index, ga_islands_launch, ga_islands_reference, ga_redraw_init
+from .sa import SaDomain, SaRun, sa_chains_init, sa_chains_launch, sa_chains_twin
 
 MAX_F, MAX_C, MAX_N = 32, 16, 1 << 24                   # the kernels' limits: F <= 32, C <= 16, N < 2^24
 # GeneticAlgorithm takes the island engine up to this many rows (search._island_engine): the largest
@@ -245,19 +246,21 @@ def ga_subset_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int,
 def sa_subset_init(tables: dict, n: int, seed: int, chain_base: int) -> np.ndarray:
     """Start subsets [n, F] int16 of 0 / 1 of global chains ``chain_base ..``
     (:func:`~avenir_amd.optimize.sa.sa_chains_init`)."""
-    from .sa import sa_chains_init
     return sa_chains_init(np.full(tables["F"], 2, dtype=np.int64), lambda s: ga_subset_valid(tables, pack_masks(s)),
                           n, seed, chain_base)
 
 
-def sa_subset_reference(tables: dict, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float,
-                        interval: int, geometric: bool, max_retry: int, seed: int, offset: int = 0, it_begin: int = 0,
-                        temp_start=None, best=None, best_cost=None, chain_base: int = 0):
-    """Host twin of ``sa_subset_kernel``: the chain frame of :mod:`~avenir_amd.optimize.sa` over 32-bit
-    masks — a move flips one bit (the value word is unused), a mask is valid inside the size range and
-    costs ``(float)errors / (float)N``.  A mask is scored once per call.  Returns (best int16 0 / 1 rows,
-    best_cost, stats, sol int16, cost, temperature)."""
-    from .sa import SaDomain, sa_chains_reference
+def sa_subset_advance(tables: dict, sol, cost, run: SaRun, device, best=None, best_cost=None, waves_per_chain: int = 0):
+    """One segment: ``sa_subset_kernel`` on a GPU (``waves_per_chain`` = 0 lets the launcher choose; no
+    result depends on it), on the host its twin — the chain frame of :mod:`~avenir_amd.optimize.sa`
+    over 32-bit masks: a move flips one bit (the value word is unused), a mask is valid inside the
+    size range and costs ``(float)errors / (float)N``; a mask is scored once per call.  Returns (best
+    int16 0 / 1 rows, best_cost, stats, sol int16, cost, temperature)."""
+    if torch.device(device).type == "cuda":
+        from .. import _native
+        head = (*_device_tables(tables, device), tables["min_size"], tables["max_size"])
+        return sa_chains_launch(_native.C().sa_subset, head, (int(waves_per_chain),), sol, cost, run, best, best_cost,
+                                device)
     F, N = tables["F"], _F(tables["N"])
     seen: dict = {}
 
@@ -269,32 +272,30 @@ def sa_subset_reference(tables: dict, sol: np.ndarray, cost: np.ndarray, iters: 
 
     dom = SaDomain(propose=lambda s, x, y: s ^ (np.uint32(1) << _unit_index(u32_to_unit(x), F).astype(np.uint32)),
                    valid=lambda s: ga_subset_valid(tables, s), price=price)
-    b, bc, st, s, c, temp = sa_chains_reference(
-        dom, pack_masks(sol), cost, iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start,
-        None if best is None else pack_masks(best), best_cost, chain_base)
+    b, bc, st, s, c, temp = sa_chains_twin(dom, pack_masks(sol), cost, run, None if best is None else pack_masks(best),
+                                           best_cost)
     return unpack_masks(b, F), bc, st, unpack_masks(s, F), c, temp
+
+
+def sa_subset_reference(tables: dict, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float,
+                        interval: int, geometric: bool, max_retry: int, seed: int, offset: int = 0, it_begin: int = 0,
+                        temp_start=None, best=None, best_cost=None, chain_base: int = 0):
+    """Host twin of ``sa_subset_kernel`` (:func:`sa_subset_advance` on the host)."""
+    return sa_subset_advance(tables, sol, cost, SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset,
+                                                      it_begin, temp_start, chain_base), "cpu", best, best_cost)
 
 
 def sa_subset_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: float, cool: float, interval: int,
                   geometric: bool, max_retry: int, seed: int, device, offset: int = 0, it_begin: int = 0,
                   temp_start=None, best=None, best_cost=None, chain_base: int = 0, waves_per_chain: int = 0):
-    """Advance the chains ``iters`` moves (from move ``it_begin``) on ``device``: the kernel on the GPU
-    (``waves_per_chain`` = 0 lets the launcher choose; no result depends on it), the twin on the host.
-    ``domain`` is a FeatureSubsetDomain or its :func:`subset_tables`.  Returns numpy (best int16,
-    best_cost, stats, sol int16, cost, temperature)."""
+    """Advance the chains ``iters`` moves (from move ``it_begin``) on ``device``: the kernel on the GPU,
+    the twin on the host.  ``domain`` is a FeatureSubsetDomain or its :func:`subset_tables`.  Returns
+    numpy (best int16, best_cost, stats, sol int16, cost, temperature)."""
     tables = domain if isinstance(domain, dict) else subset_tables(domain)
     if tables is None:
         raise ValueError("the domain is outside the subset kernel's limits")
     sol = np.ascontiguousarray(sol, dtype=np.int16)
     if sol.ndim != 2 or sol.shape[1] != tables["F"]:
         raise ValueError("sol must be [chains, F]")
-    device = torch.device(device)
-    if device.type == "cuda":
-        from .. import _native
-        from .sa import sa_chains_launch
-        head = (*_device_tables(tables, device), tables["min_size"], tables["max_size"])
-        return sa_chains_launch(_native.C().sa_subset, head, (int(waves_per_chain),), sol, cost, iters, t0, cool,
-                                interval, geometric, max_retry, seed, offset, it_begin, temp_start, best, best_cost,
-                                chain_base, device)
-    return sa_subset_reference(tables, sol, cost, iters, t0, cool, interval, geometric, max_retry, seed, offset,
-                               it_begin, temp_start, best, best_cost, chain_base)
+    run = SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, chain_base)
+    return sa_subset_advance(tables, sol, cost, run, device, best, best_cost, waves_per_chain)

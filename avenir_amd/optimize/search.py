@@ -42,11 +42,10 @@ from typing import Callable, Sequence
 import numpy as np
 import torch
 
-from .. import _native
-from ..ops.random import philox4x32, u32_to_unit
 from ..parallel.comm import Comm, get_comm
 from ..utils.resilience import IterationLoop, RecoveryConfig
 from .domain import AssignmentDomain, SearchDomain
+from .sa import SaRun, sa_assign_advance, sa_assign_init, sa_assign_reference  # noqa: F401 (the twin is re-exported)
 
 
 @dataclass
@@ -84,31 +83,27 @@ def _global_best(comm: Comm, cost: torch.Tensor, sol: torch.Tensor) -> tuple[tor
 # ================================================================================================
 class _Chains:
     """A chain engine: one of the chain kernels of optim.hip on a GPU, its host twin on the CPU.
-    ``names`` are the (GPU, CPU) engine names of ``OptResult.stats``; ``init(n, seed, chain_base)``
-    draws start solutions, ``price(sol)`` is their cost and ``run`` advances them (numpy in and out,
-    as ``ga_meeting.sa_meeting_run``)."""
+    ``names`` are the (GPU, CPU) engine names of ``OptResult.stats`` (None: no entry);
+    ``init(n, seed, chain_base)`` draws start solutions, ``price(sol)`` is their cost (numpy or tensors)
+    and ``run(sol, cost, SaRun, device, best, best_cost)`` advances them (``ga_meeting.sa_meeting_advance``)."""
 
     def __init__(self, names, init, price, run):
         self.names, self.init, self.price, self.run = names, init, price, run
 
-    def name(self, device) -> str:
-        return self.names[0] if device.type == "cuda" else self.names[1]
-
     def start(self, device, n: int, seed: int, chain_base: int) -> torch.Tensor:
-        return torch.from_numpy(self.init(n, seed, chain_base).astype(np.int64)).to(device)
+        return torch.as_tensor(self.init(n, seed, chain_base)).long().to(device)
 
     def cost(self, device, sol: torch.Tensor) -> torch.Tensor:
-        return torch.from_numpy(np.asarray(self.price(sol.cpu().numpy()), dtype=np.float32)).to(device)
+        return torch.as_tensor(self.price(sol), dtype=torch.float32).to(device)
 
-    def advance(self, device, sol, cost, iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin=0,
-                temp_start=None, best=None, best_cost=None, return_state=True, chain_base=0):
-        """The signature and the results of :func:`sa_assign` with ``return_state``, on ``device``."""
-        host = lambda t: None if t is None else t.detach().cpu().numpy()
-        b, bc, stats, s, c, temp = self.run(host(sol), host(cost), iters, t0, cool, interval, geometric, max_retry,
-                                            seed, device, offset, it_begin, temp_start, host(best), host(best_cost),
-                                            chain_base)
-        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
-        return dev(b).long(), dev(bc), stats, dev(s).long(), dev(c), float(temp)
+    def advance(self, device, sol, cost, run: SaRun, best=None, best_cost=None):
+        """Tensors on ``device`` in and out; a kernel takes them where they are, a host twin as numpy."""
+        state = [sol, cost, best, best_cost]
+        if device.type != "cuda":
+            state = [None if t is None else t.detach().numpy() for t in state]
+        b, bc, stats, s, c, temp = self.run(*state[:2], run, device, *state[2:])
+        return (torch.as_tensor(b).long(), torch.as_tensor(bc), stats, torch.as_tensor(s).long(), torch.as_tensor(c),
+                float(temp))
 
 
 class SimulatedAnnealing:
@@ -149,12 +144,10 @@ class SimulatedAnnealing:
     def run(self, init: torch.Tensor | None = None) -> OptResult:
         comm = self.comm or get_comm()
         d = self.domain
-        kernel_ok = isinstance(d, AssignmentDomain) and self.step == 1 and d.L <= 512
-        use_kernel = kernel_ok if self.use_kernel is None else (self.use_kernel and kernel_ok)
-        engine = None if isinstance(d, AssignmentDomain) else self._chain_engine()
+        engine = self._chain_engine(comm.world)
         chain_base = None
-        if use_kernel or engine is not None:
-            best, bc, stats, gen, chain_base = self._run_kernel(comm, init, engine)
+        if engine is not None:
+            best, bc, stats, chain_base = self._run_kernel(comm, init, engine)
         else:
             seed = self.seed + 1_000_003 * comm.rank
             gen = _gen(d.device, seed)
@@ -177,11 +170,12 @@ class SimulatedAnnealing:
         b, c = _global_best(comm, bc, best)
         return OptResult(b, c, bc, best, stats=stats)
 
-    def _chain_engine(self):
-        """The one-launch chain kernel that applies to a domain other than an assignment domain, or
-        None (the generic torch path): single-position moves and no tied groups.  A
-        MeetingScheduleDomain within ``meeting_tables``' limits takes ``sa_meeting_kernel``
-        (optimize/ga_meeting.py), a FeatureSubsetDomain with the built-in naive-Bayes evaluator within
+    def _chain_engine(self, world: int = 1):
+        """The one-launch chain kernel that applies to the domain, or None (the generic torch path):
+        single-position moves and no tied groups.  An AssignmentDomain of L <= 512 positions takes
+        ``sa_assign_kernel`` or, on the CPU, its twin unless ``use_kernel`` is False.  A MeetingScheduleDomain
+        within ``meeting_tables``' limits takes ``sa_meeting_kernel`` (optimize/ga_meeting.py), a
+        FeatureSubsetDomain with the built-in naive-Bayes evaluator within
         ``subset_tables``' limits takes ``sa_subset_kernel`` (optimize/ga_subset.py) — on a GPU by
         default, on the CPU (their host twins) only when ``use_kernel`` is True, so CPU default
         results are unchanged.  Measured against the generic path on one MI355X
@@ -193,26 +187,28 @@ class SimulatedAnnealing:
         generic and ``use_kernel=True`` still forces the engine.  The state of a chain is explicit,
         so the engines work with ``recovery``."""
         d = self.domain
-        if self.use_kernel is False or self.step != 1 or getattr(d, "groups", None):
+        if self.use_kernel is False or self.step != 1:
             return None
-        if not (self.use_kernel is True or d.device.type == "cuda"):
+        if isinstance(d, AssignmentDomain):
+            return _assign_chains(d, self.n_chains * world) if d.L <= 512 else None
+        if getattr(d, "groups", None) or not (self.use_kernel is True or d.device.type == "cuda"):
             return None
         from . import ga_meeting as gm, ga_subset as gs
         tb = gm.meeting_tables(d)           # None unless a MeetingScheduleDomain within the kernel's limits
         if tb is not None and gm.sa_meeting_lds(tb["M"]) <= 64 * 1024:
             return _Chains(("sa_meeting_kernel", "sa_meeting_twin"), partial(gm.sa_meeting_init, tb),
-                           partial(gm.ga_meeting_price, tb), partial(gm.sa_meeting_run, tb))
+                           lambda s: gm.ga_meeting_price(tb, s.cpu().numpy()), partial(gm.sa_meeting_advance, tb))
         if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3:
             tb = gs.subset_tables(d)        # None unless a FeatureSubsetDomain with the built-in evaluator
             # one chain is one workgroup streaming every row once per move: by default up to
             # ga_subset.SA_ROW_CAP rows, where a single chain still beats the generic path
             if tb is not None and (self.use_kernel is True or tb["N"] <= gs.SA_ROW_CAP):
                 return _Chains(("sa_subset_kernel", "sa_subset_host"), partial(gs.sa_subset_init, tb),
-                               lambda s: gs.ga_subset_price(tb, gs.pack_masks(s), d.device),
-                               partial(gs.sa_subset_run, tb))
+                               lambda s: gs.ga_subset_price(tb, gs.pack_masks(s.cpu().numpy()), d.device),
+                               partial(gs.sa_subset_advance, tb))
         return None
 
-    def _run_kernel(self, comm, init, engine=None):
+    def _run_kernel(self, comm, init, engine):
         """K22 path.  Chains are GLOBAL: chain ``g`` draws Philox stream ``(seed, g)`` and starts from
         row ``g`` of one population drawn from ``seed`` alone, rank ``r`` runs chains
         ``[r * n_chains, (r + 1) * n_chains)``.  The W-rank result therefore equals one process
@@ -220,13 +216,10 @@ class SimulatedAnnealing:
         ANY world size: the restored chains are re-dealt by global index.  Under checkpointing the
         run is split into segments of ``segment`` moves (one launch each, same Philox counters and
         cooling schedule as one launch).  ``engine`` (:meth:`_chain_engine`) supplies the start
-        solutions, their price and the launch for a meeting-schedule or feature-subset domain;
-        without it the domain is an assignment domain (``sa_assign``)."""
+        solutions, their price and the launch."""
         from ..data.table import shard_range
         d = self.domain
         W, r = comm.world, comm.rank
-        gen = None                                               # local search: per global chain (run)
-        advance = partial(sa_assign, d) if engine is None else partial(engine.advance, d.device)
         stats = {"better": 0, "worse_accepted": 0, "rejected": 0}
         best = bc = temp = None
         b0 = 0
@@ -243,25 +236,21 @@ class SimulatedAnnealing:
                 if init is None:
                     total = self.n_chains * W
                     a = r * self.n_chains
-                    if engine is None:
-                        sol = d.random(total, _gen(d.device, self.seed))[0][a:a + self.n_chains]
-                    else:                                        # per global chain: no rank draws the others'
-                        sol = engine.start(d.device, self.n_chains, self.seed, a)
+                    sol = engine.start(d.device, self.n_chains, self.seed, a)
                 else:
                     sol = init.to(d.device).long().clone()
                     counts = comm.all_gather(torch.tensor([sol.shape[0]])).view(-1).tolist()
                     total, a = sum(counts), sum(counts[:r])
                 # the engines price with their own arithmetic: the current cost is always the kernel's
                 # price of the solution, the same bits on either device
-                cost = d.evaluate(sol) if engine is None else engine.cost(d.device, sol)
+                cost = engine.cost(d.device, sol)
             seg = max(1, self.segment or -(-self.iters // 10)) if lp.enabled else max(1, self.iters)
             for b in range(b0, self.iters, seg):
                 n = min(seg, self.iters - b)
                 with lp.step(b // seg):
-                    best, bc, s, sol, cost, temp = advance(sol, cost, n, self.t0, self.cooling, self.interval,
-                                                           self.geometric, self.max_retry, self.seed, 0, it_begin=b,
-                                                           temp_start=temp, best=best, best_cost=bc,
-                                                           return_state=True, chain_base=a)
+                    run = SaRun(n, self.t0, self.cooling, self.interval, self.geometric, self.max_retry, self.seed,
+                                it_begin=b, temp_start=temp, chain_base=a)
+                    best, bc, s, sol, cost, temp = engine.advance(d.device, sol, cost, run, best, bc)
                 for k in stats:
                     stats[k] += s[k]
                 if lp.enabled:
@@ -272,9 +261,9 @@ class SimulatedAnnealing:
         if best is None:                                   # no moves at all
             best, bc = sol.clone(), cost.clone()
         stats = self._global_stats(comm, stats)
-        if engine is not None:
-            stats["engine"] = engine.name(d.device)
-        return best.long(), bc, stats, gen, a
+        if engine.names:
+            stats["engine"] = engine.names[0 if d.device.type == "cuda" else 1]
+        return best.long(), bc, stats, a
 
     @staticmethod
     def _global_stats(comm, stats: dict) -> dict:
@@ -321,122 +310,23 @@ class SimulatedAnnealing:
         return best, bc, stats
 
 
+def _assign_chains(d: AssignmentDomain, total: int | None = None) -> _Chains:
+    """``sa_assign_kernel`` and its twin (optimize/sa.py); the starts are rows of one population of ``total`` chains."""
+    return _Chains(None, partial(sa_assign_init, d, total=total), d.evaluate, partial(sa_assign_advance, d))
+
+
 def sa_assign(d: AssignmentDomain, sol: torch.Tensor, cost: torch.Tensor, iters: int, t0: float, cool: float,
               interval: int, geometric: bool, max_retry: int, seed: int, offset: int, it_begin: int = 0,
               temp_start: float | None = None, best: torch.Tensor | None = None, best_cost: torch.Tensor | None = None,
               return_state: bool = False, chain_base: int = 0):
-    """Run ``sol.shape[0]`` SA chains over an assignment domain: K22 kernel on GPU, the bit-exact
-    numpy mirror (same Philox stream, float32 arithmetic) on CPU.  Returns (best_sol, best_cost, stats)
+    """Run ``sol.shape[0]`` SA chains over an assignment domain: K22 kernel on GPU, its numpy twin
+    (same Philox stream, float32 arithmetic) on CPU.  Returns (best_sol, best_cost, stats)
     or, with ``return_state``, also (current_sol, current_cost, temperature) so a run split into
     segments [it_begin, it_begin + iters) (checkpoint / resume) equals one uninterrupted launch.
     Row ``p`` is global chain ``chain_base + p``: its Philox stream does not depend on the launch."""
-    ts = float(t0 if temp_start is None else temp_start)
-    if sol.device.type == "cuda":
-        s16 = sol.to(torch.int16).contiguous()
-        cur = cost.float().contiguous().clone()
-        bsol = s16.clone() if best is None else best.to(torch.int16).contiguous().clone()
-        bc = cur.clone() if best_cost is None else best_cost.float().contiguous().clone()
-        st = torch.zeros(4, dtype=torch.long, device=sol.device)
-        _native.C().sa_assign(d.cost_table, None if d.conflict is None else d.conflict.to(torch.uint8).contiguous(),
-                              bool(d.swap_moves), s16, cur, bsol, bc, int(iters), float(t0), float(cool),
-                              int(interval), bool(geometric), int(max_retry), int(seed), int(offset), st,
-                              int(it_begin), ts, int(chain_base))
-        s = st.tolist()
-        stats = {"better": s[0], "worse_accepted": s[1], "rejected": s[2]}
-        if return_state:
-            temp = float(np.array([s[3]], dtype=np.uint32).view(np.float32)[0]) if iters > 0 else ts
-            return bsol.long(), bc, stats, s16.long(), cur, temp
-        return bsol.long(), bc, stats
-    out = sa_assign_reference(d.cost_table.numpy(), None if d.conflict is None else d.conflict.numpy(),
-                              d.swap_moves, sol.numpy(), cost.float().numpy(), iters, t0, cool, interval,
-                              geometric, max_retry, seed, offset, it_begin, ts,
-                              None if best is None else best.numpy(), None if best_cost is None else best_cost.float().numpy(),
-                              chain_base)
-    b, c, s, cs, cc, temp = out
-    if return_state:
-        return (torch.from_numpy(b).long(), torch.from_numpy(c), s, torch.from_numpy(cs).long(),
-                torch.from_numpy(cc), float(temp))
-    return torch.from_numpy(b).long(), torch.from_numpy(c), s
-
-
-def sa_assign_reference(cost, conflict, swap, sol, cur, iters, t0, cool, interval, geometric, max_retry, seed, offset,
-                        it_begin=0, temp_start=None, best=None, best_cost=None, chain_base=0):
-    """Host mirror of ``sa_assign_kernel`` (optim.hip), vectorised over chains.  Returns
-    (best, best_cost, stats, current_sol, current_cost, temperature)."""
-    cost = np.asarray(cost, np.float32)
-    L, V = cost.shape
-    sol = np.array(sol, dtype=np.int64)
-    P = sol.shape[0]
-    c = np.array(cur, dtype=np.float32)
-    bc = c.copy() if best_cost is None else np.array(best_cost, dtype=np.float32)
-    best = sol.copy() if best is None else np.array(best, dtype=np.int64)
-    rows = np.arange(P)
-    idx = np.arange(P, dtype=np.uint64) + np.uint64(chain_base)
-    ar = np.arange(L)
-    invL = np.float32(1.0 / L)
-    temp = np.float32(t0 if temp_start is None else temp_start)
-    st = [0, 0, 0]
-    R = max_retry + 1
-    for it in range(it_begin, it_begin + iters):
-        pending = np.ones(P, bool)
-        pos = np.full(P, -1)
-        nv = np.zeros(P, np.int64)
-        old = np.zeros(P, np.int64)
-        j2 = np.full(P, -1)
-        for tr in range(R):
-            if not pending.any():
-                break
-            x, y, _, _ = philox4x32(seed, offset + it * R + tr, idx)
-            cp = np.minimum((u32_to_unit(x) * np.float32(L)).astype(np.int64), L - 1)
-            cv = np.minimum((u32_to_unit(y) * np.float32(V - 1)).astype(np.int64), V - 2)
-            ov = sol[rows, cp]
-            cv = cv + (cv >= ov)
-            if swap:
-                holder = (sol == cv[:, None]) & (ar[None, :] != cp[:, None])
-                sw = np.where(holder.any(1), holder.argmax(1), -1)
-            else:
-                sw = np.full(P, -1)
-            cand = sol.copy()
-            cand[rows, cp] = cv
-            hs = sw >= 0
-            cand[rows[hs], sw[hs]] = ov[hs]
-            if conflict is not None:
-                bad = ((cand == cv[:, None]) & (ar[None, :] != cp[:, None]) & conflict[cp]).any(1)
-                swr = np.where(hs, sw, 0)
-                bad2 = ((cand == ov[:, None]) & (ar[None, :] != swr[:, None]) & conflict[swr]).any(1) & hs
-                ok = ~(bad | bad2)
-            else:
-                ok = np.ones(P, bool)
-            take = pending & ok
-            sol[take] = cand[take]
-            pos[take], nv[take], old[take], j2[take] = cp[take], cv[take], ov[take], sw[take]
-            pending &= ~ok
-        moved = pos >= 0
-        pp = np.where(moved, pos, 0)
-        delta = cost[pp, nv] - cost[pp, old]
-        jj = np.where(j2 >= 0, j2, 0)
-        delta = np.where(j2 >= 0, delta + (cost[jj, old] - cost[jj, nv]), delta).astype(np.float32)
-        delta = (delta * invL).astype(np.float32)
-        x2, _, _, _ = philox4x32(seed ^ 0x9E3779B97F4A7C15, offset + it, idx)
-        with np.errstate(over="ignore"):
-            pr = np.exp(-delta / np.maximum(temp, np.float32(1e-12))).astype(np.float32)
-        acc = moved & ((delta <= 0) | (u32_to_unit(x2) < pr))
-        rej = moved & ~acc
-        st[0] += int((acc & (delta <= 0)).sum())
-        st[1] += int((acc & (delta > 0)).sum())
-        st[2] += int(rej.sum())
-        r = rows[rej]
-        sol[r, pos[rej]] = old[rej]
-        hj = rej & (j2 >= 0)
-        sol[rows[hj], j2[hj]] = nv[hj]
-        c = np.where(acc, (c + delta).astype(np.float32), c)
-        imp = acc & (c < bc)
-        best[imp] = sol[imp]
-        bc = np.where(imp, c, bc)
-        if interval > 0 and (it + 1) % interval == 0:
-            temp = np.float32(temp * np.float32(cool)) if geometric else np.float32(max(t0 - (it + 1) * cool, 1e-12))
-    return (best, bc.astype(np.float32), {"better": st[0], "worse_accepted": st[1], "rejected": st[2]},
-            sol, c.astype(np.float32), temp)
+    run = SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, chain_base)
+    out = _assign_chains(d).advance(sol.device, sol, cost, run, best, best_cost)
+    return out if return_state else out[:3]
 
 
 def local_focussed(d: SearchDomain, sols: torch.Tensor, costs: torch.Tensor, n_iter: int, gen=None):

@@ -12,6 +12,7 @@ import torch
 
 from avenir_amd.optimize.domains import MeetingScheduleDomain
 from tests._dist import run_world_outcome
+from tests._sa import meeting_start as _start, state_equal as _state_equal
 
 
 @functools.lru_cache(maxsize=None)
@@ -29,20 +30,6 @@ def _one_minute():
     d = MeetingScheduleDomain(parts, (src.dur / 60).tolist(), 10, src.ordered, src.blocked, src.role_w.tolist(),
                               minutes=(0,))
     return d, meeting_tables(d)
-
-
-def _start(tb, n, seed, base):
-    from avenir_amd.optimize.ga_meeting import ga_meeting_price, sa_meeting_init
-    sol = sa_meeting_init(tb, n, seed, base)
-    return sol, ga_meeting_price(tb, sol)
-
-
-def _state_equal(a, b):
-    """(best, best_cost, stats, sol, cost, temperature) bit for bit."""
-    for i in (0, 1, 3, 4):
-        assert a[i].dtype == b[i].dtype and np.array_equal(a[i], b[i]), i
-    assert a[2] == b[2]
-    assert np.float32(a[5]).view(np.uint32) == np.float32(b[5]).view(np.uint32)
 
 
 # ------------------------------------------------------------------------------------------- CPU

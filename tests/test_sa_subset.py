@@ -12,6 +12,7 @@ import torch
 
 from avenir_amd.optimize.domains import FeatureSubsetDomain
 from tests._dist import run_world_outcome
+from tests._sa import subset_start as _start, state_equal as _state_equal
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,20 +49,6 @@ def _tables(case):
     tb = subset_tables(d)
     assert tb is not None
     return d, tb
-
-
-def _start(tb, n, seed, base):
-    from avenir_amd.optimize.ga_subset import ga_subset_price, pack_masks, sa_subset_init
-    sol = sa_subset_init(tb, n, seed, base)
-    return sol, ga_subset_price(tb, pack_masks(sol))
-
-
-def _state_equal(a, b):
-    """(best, best_cost, stats, sol, cost, temperature) bit for bit."""
-    for i in (0, 1, 3, 4):
-        assert a[i].dtype == b[i].dtype and np.array_equal(a[i], b[i]), i
-    assert a[2] == b[2]
-    assert np.float32(a[5]).view(np.uint32) == np.float32(b[5]).view(np.uint32)
 
 
 def _check(d, tb, sol, cost):
