@@ -1704,6 +1704,63 @@ void sa_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tens
                  cur_stream(LL));
 }
 
+// Tabu search over an assignment domain (optim.hip::tabu_assign_kernel): cost [L, V], conflict [L, L]
+// uint8 or None; the chains' state sol / best_sol int16 [P, L], cur_cost / best_cost [P], tabu int32
+// [P, L, V] in and out; hist [P, iters] out; stats[0..2] += moves, stalls, aspirated.  The caller
+// guarantees solution values in [0, V) (optimize/tabu.py::tabu_assign_advance checks them).
+void tabu_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, at::Tensor& sol,
+                 at::Tensor& cur_cost, at::Tensor& best_sol, at::Tensor& best_cost, at::Tensor& tabu, at::Tensor& hist,
+                 int64_t iters, int64_t tenure, int64_t it_begin, at::Tensor& stats) {
+  CHECK_DEV(cost);
+  CHECK_DTYPE(cost, at::kFloat);
+  TORCH_CHECK(cost.dim() == 2 && cost.size(0) >= 1 && cost.size(0) < (1LL << 31) && cost.size(1) >= 1 &&
+                  cost.size(1) <= 32767, "tabu_assign: cost must be [L >= 1, 1 <= V <= 32767]");
+  const int64_t L = cost.size(0), V = cost.size(1);
+  TORCH_CHECK(iters >= 0 && tenure >= 0 && it_begin >= 0 && iters < (1LL << 31) && tenure < (1LL << 31) &&
+              it_begin < (1LL << 31) && it_begin + iters + tenure < (1LL << 31),
+              "tabu_assign: 0 <= iters, tenure, it_begin and it_begin + iters + tenure < 2^31");
+  for (const at::Tensor* t : {&sol, &best_sol}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kShort);
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == L, "tabu_assign: sol and best_sol must be [P, ", L, "]");
+  }
+  const int64_t P = sol.size(0);
+  TORCH_CHECK(best_sol.size(0) == P && P < (1LL << 31), "tabu_assign: best_sol must have the shape of sol, P < 2^31");
+  for (const at::Tensor* t : {&cur_cost, &best_cost}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kFloat);
+    TORCH_CHECK(t->dim() == 1 && t->numel() == P, "tabu_assign: cost vectors must be [P]");
+  }
+  CHECK_DEV(tabu);
+  CHECK_DTYPE(tabu, at::kInt);
+  TORCH_CHECK(tabu.dim() == 3 && tabu.size(0) == P && tabu.size(1) == L && tabu.size(2) == V,
+              "tabu_assign: tabu must be [P, L, V]");
+  CHECK_DEV(hist);
+  CHECK_DTYPE(hist, at::kFloat);
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) == P && hist.size(1) == iters, "tabu_assign: hist must be [P, iters]");
+  CHECK_DEV(stats);
+  CHECK_DTYPE(stats, at::kLong);
+  TORCH_CHECK(stats.numel() == 4, "tabu_assign: stats must hold 4 entries");
+  for (const at::Tensor* t : {&sol, &cur_cost, &best_sol, &best_cost, &tabu, &hist, &stats})
+    TORCH_CHECK(t->device() == cost.device(), "tabu_assign: tensors on one device");
+  const uint8_t* cf = nullptr;
+  if (conflict.has_value() && conflict->defined()) {
+    CHECK_DEV((*conflict));
+    CHECK_DTYPE((*conflict), at::kByte);
+    TORCH_CHECK(conflict->dim() == 2 && conflict->size(0) == L && conflict->size(1) == L &&
+                    conflict->device() == cost.device(), "tabu_assign: conflict must be [L, L] on the device of cost");
+    cf = conflict->data_ptr<uint8_t>();
+  }
+  TORCH_CHECK(avk::tabu_assign_lds((int)L, (int)V) <= avk::TABU_LDS_LIMIT, "tabu_assign: the tables of a chain (",
+              avk::tabu_assign_lds((int)L, (int)V), " bytes) exceed 64 KiB of LDS");
+  if (P == 0 || iters == 0) return;
+  DevGuard g(cost.device());
+  avk::tabu_assign(cost.data_ptr<float>(), (int)L, (int)V, cf, sol.data_ptr<int16_t>(), cur_cost.data_ptr<float>(),
+                   best_sol.data_ptr<int16_t>(), best_cost.data_ptr<float>(), tabu.data_ptr<int>(),
+                   hist.data_ptr<float>(), (int)P, (long long)iters, (long long)it_begin, (long long)tenure,
+                   reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), cur_stream(cost));
+}
+
 // ---------------------------------------------------------------------------------------------
 // generalised linear models (K13)
 // ---------------------------------------------------------------------------------------------
@@ -4531,6 +4588,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("ga_meeting_lds", [](int64_t P, int64_t L, int64_t r) { return (int64_t)avk::ga_meeting_lds((int)P, (int)L, (int)r); });
   m.def("subset_errors", &subset_errors);
   m.def("ga_subset", &ga_subset);
+  m.def("tabu_assign", &tabu_assign);
+  m.def("tabu_assign_lds", [](int64_t L, int64_t V) { return (int64_t)avk::tabu_assign_lds((int)L, (int)V); });
   m.def("sa_meeting", &sa_meeting);
   m.def("sa_meeting_lds", [](int64_t M) { return (int64_t)avk::sa_meeting_lds((int)M); });
   m.def("sa_subset", &sa_subset);

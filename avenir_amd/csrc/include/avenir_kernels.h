@@ -182,6 +182,21 @@ SaSubsetPlan sa_subset_plan(int N, int F, int C, int P, int waves_per_chain);
 void sa_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
                int max_size, short* sol, float* cur_cost, short* best_sol, float* best_cost, int P, const SaRun& run,
                unsigned long long* stats, int waves_per_chain, hipStream_t stream);
+// Tabu search over an assignment domain (one launch, resumable; tabu_assign_kernel, one chain per
+// wave): sol / best_sol int16 [P][L], cur_cost / best_cost [P] and tabu int32 [P][L][V] in and out
+// (tabu[l][v] = the first iteration at which the move is free again, -1 when fresh), hist [P][iters]
+// = the best cost after every iteration, stats[0..2] += moves, stalls, aspirated.  Iterations
+// [it_begin, it_begin + iters), it_begin + iters + tenure < 2^31; every sol value in [0, V).
+constexpr size_t TABU_LDS_LIMIT = 64 * 1024;
+struct TabuPlan {
+  int waves, staged;  // chains per workgroup; cost and conflict tables copied to LDS
+  size_t lds;         // bytes of dynamic LDS per workgroup (above TABU_LDS_LIMIT: no launch)
+};
+TabuPlan tabu_assign_plan(int L, int V);
+size_t tabu_assign_lds(int L, int V);
+void tabu_assign(const float* cost, int L, int V, const uint8_t* conflict, short* sol, float* cur_cost,
+                 short* best_sol, float* best_cost, int* tabu, float* hist, int P, long long iters, long long it_begin,
+                 long long tenure, unsigned long long* stats, hipStream_t stream);
 
 // ---- linear.hip (K13) ----------------------------------------------------------------------
 int glm_grid(long long n);

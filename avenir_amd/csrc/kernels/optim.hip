@@ -1,6 +1,7 @@
 // K22: stochastic search in persistent launches (CDNA4, gfx950) — island genetic algorithms and
 // simulated-annealing chains over three domains each: assignments (a [L][V] cost table and an
-// [L][L] conflict table), meeting schedules and feature subsets scored by naive Bayes.
+// [L][L] conflict table), meeting schedules and feature subsets scored by naive Bayes; and tabu
+// search over assignments (tabu_assign_kernel, one chain per wave, at the end of the kernels).
 //
 // Reference: one SA chain or one GA per Spark partition, mutating string-encoded solutions through
 // the BasicSearchDomain SPI (S/optimize/SimulatedAnnealing.scala:111-187,
@@ -1073,6 +1074,188 @@ __global__ __launch_bounds__(1024) void sa_subset_kernel(
   }
 }
 
+// ---- tabu search over assignments: one chain per wave, all iterations in one launch -------------
+// Reference: the tenure purge of TabuSearchDomain (J/optimize/TabuSearchDomain.java:54-66) over the
+// full single-reassignment neighbourhood.  A chain's state is its solution, the solution's cost, the
+// best solution and cost, and tabu[l][v] = the first iteration at which moving position l to value
+// v is free again.  Iteration `it`:
+//   1. every cell (l, v) is priced nc = cost + ((C[l][v] - C[l][sol[l]]) / (float)L), each operation
+//      rounded on its own (an IEEE division, not a product with 1 / L);
+//   2. a cell is bad when v == sol[l] or a position j != l with conflict[l][j] holds v;
+//   3. it is admissible when not bad and (tabu[l][v] <= it or nc < the best cost at the
+//      iteration's start: aspiration);
+//   4. the move is the admissible cell of smallest nc < +inf, ties to the smallest l V + v;
+//   5. a move sets tabu[l][sol[l]] = it + tenure, sol[l] = v, cost = nc (moves, and aspirated when
+//      the cell was tabu); without one the chain stalls;
+//   6. a cost below the best replaces the best;  7. hist[p][it - it_begin] = the best cost.
+// Nothing is drawn, so optimize/tabu.py::tabu_assign_reference equals the kernel bit for bit.
+// A wave keeps in LDS, per chain: the tabu table, cnt[l][v] = the number of j != l with
+// conflict[l][j] and sol[j] == v (validity of a cell is one read; a move updates one column of it,
+// lane j the row of position j), the solution and cur[l] = C[l][sol[l]].  The 4, 2 or 1 waves of a
+// workgroup share an LDS copy of C and of the transposed conflict table (STAGED; avk::
+// tabu_assign_plan); where those do not fit, one wave per workgroup reads both from global memory.
+// Lanes walk the L V cells in steps of 64 carrying (l, v), each keeps its best cell as one 64-bit
+// key — the order-preserving image of nc's bits above the flat index — and the wave minimum of the
+// keys (DPP + v_readlane) is the move.  The chain loop holds no workgroup barrier: LDS runs one
+// wave's instructions in order, so a wave's reads see its earlier writes.
+constexpr unsigned long long TB_NONE = ~0ull;
+
+// monotone float -> unsigned, both zeros to one key
+__device__ __forceinline__ unsigned tb_key(float f) {
+  const unsigned u = __float_as_uint(f == 0.f ? 0.f : f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+template <int CTRL>
+__device__ __forceinline__ unsigned long long tb_min_step(unsigned long long v) {
+  const unsigned lo = (unsigned)av::dpp_i<CTRL>((int)(unsigned)v);
+  const unsigned hi = (unsigned)av::dpp_i<CTRL>((int)(unsigned)(v >> 32));
+  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+  return o < v ? o : v;
+}
+__device__ __forceinline__ unsigned long long tb_readlane(unsigned long long v, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// wave minimum of 64-bit keys, wave-uniform (all 64 lanes active)
+__device__ __forceinline__ unsigned long long tb_wave_min(unsigned long long v) {
+  v = tb_min_step<0xB1>(v);
+  v = tb_min_step<0x4E>(v);
+  v = tb_min_step<0x124>(v);
+  v = tb_min_step<0x128>(v);
+  const unsigned long long a = tb_readlane(v, 0), b = tb_readlane(v, 16), c = tb_readlane(v, 32), d = tb_readlane(v, 48);
+  const unsigned long long ab = a < b ? a : b, cd = c < d ? c : d;
+  return ab < cd ? ab : cd;
+}
+
+__host__ __device__ constexpr size_t tb_chain_bytes(size_t L, size_t V) {
+  return ga_a16(4 * L * V) + ga_a16(4 * L) + ga_a16(2 * L * V) + ga_a16(2 * L);  // tabu, cur, cnt, sol
+}
+__host__ __device__ constexpr size_t tb_shared_bytes(size_t L, size_t V) { return ga_a16(4 * L * V) + ga_a16(L * L); }
+
+template <bool STAGED>
+__global__ __launch_bounds__(256) void tabu_assign_kernel(
+    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, short* __restrict__ sol,
+    float* __restrict__ cur_cost, short* __restrict__ best_sol, float* __restrict__ best_cost, int* __restrict__ tabu,
+    float* __restrict__ hist, int P, int iters, int it_begin, int tenure, unsigned long long* __restrict__ stats) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char tb_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+  const int LV = L * V;
+  const long long p = (long long)blockIdx.x * W + wave;
+  unsigned char* at = tb_lds;
+  const float* C = cost;
+  const uint8_t* cf = conflict;  // conflict[j][l] at cf[j * cj + l * cl]
+  int cj = L, cl = 1;
+  if (STAGED) {
+    float* Cs = reinterpret_cast<float*>(at);
+    uint8_t* Ts = at + ga_a16((size_t)4 * LV);
+    at += tb_shared_bytes(L, V);
+    // the waves that own a chain stage the tables; the others only keep the barrier
+    const int live = min((long long)W, (long long)P - (long long)blockIdx.x * W) * 64;
+    if ((int)threadIdx.x < live) {
+      for (int i = threadIdx.x; i < LV; i += live) Cs[i] = cost[i];
+      if (conflict)
+        for (int i = threadIdx.x; i < L * L; i += live) {
+          const int l = i / L, j = i - l * L;
+          Ts[i] = conflict[(long long)j * L + l];  // Ts[l][j] = conflict[j][l]
+        }
+    }
+    __syncthreads();
+    C = Cs;
+    cf = Ts;  // read only with a conflict table
+    cj = 1;
+    cl = L;
+  }
+  if (p >= P) return;
+  at += (size_t)wave * tb_chain_bytes(L, V);
+  int* tb = reinterpret_cast<int*>(at);                                      at += ga_a16((size_t)4 * LV);
+  float* cur = reinterpret_cast<float*>(at);                                 at += ga_a16((size_t)4 * L);
+  unsigned short* cnt = reinterpret_cast<unsigned short*>(at);               at += ga_a16((size_t)2 * LV);
+  short* s = reinterpret_cast<short*>(at);
+  short* gs = sol + p * L;
+  short* bs = best_sol + p * L;
+  int* gt = tabu + p * LV;
+  float* gh = hist + p * iters;
+  for (int j = lane; j < L; j += 64) {
+    const short x = gs[j];
+    s[j] = x;
+    cur[j] = C[j * V + x];
+  }
+  for (int i = lane; i < LV; i += 64) {
+    tb[i] = gt[i];
+    cnt[i] = 0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (conflict)  // lane l owns row l of cnt
+    for (int l = lane; l < L; l += 64)
+      for (int j = 0; j < L; ++j)
+        if (j != l && cf[(long long)l * cj + (long long)j * cl]) ++cnt[l * V + s[j]];
+  __builtin_amdgcn_wave_barrier();
+  float c = cur_cost[p], bc = best_cost[p];
+  const float Lf = (float)L;
+  const int l0 = lane / V, v0 = lane - l0 * V, dl = 64 / V, dv = 64 - dl * V;
+  unsigned long long moves = 0, stalls = 0, aspirated = 0;
+  for (int k = 0; k < iters; ++k) {
+    const int it = it_begin + k;
+    unsigned long long key = TB_NONE;
+    int bl = 0, bv = 0;
+    float bn = 0.f;
+    for (int i = lane, l = l0, v = v0; i < LV; i += 64) {
+      const float d = C[i] - cur[l];
+      const float q = d / Lf;
+      const float nc = c + q;
+      const bool bad = v == s[l] || cnt[i] != 0;
+      if (!bad && (tb[i] <= it || nc < bc) && nc < INFINITY) {
+        const unsigned long long kk = ((unsigned long long)tb_key(nc) << 32) | (unsigned)i;
+        if (kk < key) { key = kk; bl = l; bv = v; bn = nc; }
+      }
+      l += dl;
+      v += dv;
+      if (v >= V) { v -= V; ++l; }
+    }
+    key = tb_wave_min(key);
+    if (key != TB_NONE) {
+      const int i = (int)(unsigned)key;  // lane i & 63 holds the cell
+      const int l = __builtin_amdgcn_readlane(bl, i & 63), v = __builtin_amdgcn_readlane(bv, i & 63);
+      const int old = s[l];
+      aspirated += tb[i] > it ? 1 : 0;
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) {
+        tb[l * V + old] = it + tenure;
+        s[l] = (short)v;
+        cur[l] = C[i];
+      }
+      if (conflict)  // positions in conflict with l see `old` leave and v arrive
+        for (int j = lane; j < L; j += 64)
+          if (j != l && cf[(long long)j * cj + (long long)l * cl]) {
+            --cnt[j * V + old];
+            ++cnt[j * V + v];
+          }
+      c = av::lane_f(bn, i & 63);
+      ++moves;
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      ++stalls;
+    }
+    if (c < bc) {
+      bc = c;
+      for (int j = lane; j < L; j += 64) bs[j] = s[j];
+    }
+    if (lane == 0) gh[k] = bc;
+  }
+  for (int j = lane; j < L; j += 64) gs[j] = s[j];
+  for (int i = lane; i < LV; i += 64) gt[i] = tb[i];
+  if (lane == 0) {
+    cur_cost[p] = c;
+    best_cost[p] = bc;
+    if (moves) atomicAdd(&stats[0], moves);
+    if (stalls) atomicAdd(&stats[1], stalls);
+    if (aspirated) atomicAdd(&stats[2], aspirated);
+  }
+}
+
 }  // namespace
 
 namespace avk {
@@ -1238,6 +1421,38 @@ void sa_subset(const float* LL, const float* log_prior, const int* labels, int N
   if (P <= 0 || run.iters <= 0) return;
   sa_subset_kernel<<<pl.grid, pl.threads, pl.lds, stream>>>(LL, log_prior, labels, N, F, C, min_size, max_size, sol,
                                                            cur_cost, best_sol, best_cost, stats, A, pl.rows, pl.waves);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+// 4, 2 or 1 chains (waves) per workgroup beside one shared copy of the cost and conflict tables;
+// one chain per workgroup without the copy where even that does not fit
+TabuPlan tabu_assign_plan(int L, int V) {
+  const size_t per = tb_chain_bytes(L, V), shared = tb_shared_bytes(L, V);
+  for (int w = 4; w >= 1; w >>= 1)
+    if (w * per + shared <= TABU_LDS_LIMIT) return TabuPlan{w, 1, w * per + shared};
+  return TabuPlan{1, 0, per};
+}
+
+size_t tabu_assign_lds(int L, int V) { return tabu_assign_plan(L, V).lds; }
+
+void tabu_assign(const float* cost, int L, int V, const uint8_t* conflict, short* sol, float* cur_cost,
+                 short* best_sol, float* best_cost, int* tabu, float* hist, int P, long long iters, long long it_begin,
+                 long long tenure, unsigned long long* stats, hipStream_t stream) {
+  if (L < 1 || V < 1 || V > 32767) throw std::invalid_argument("tabu_assign: L >= 1, 1 <= V <= 32767");
+  if (iters < 0 || it_begin < 0 || tenure < 0 || it_begin + iters + tenure >= (1LL << 31))
+    throw std::invalid_argument("tabu_assign: 0 <= iters, it_begin, tenure and it_begin + iters + tenure < 2^31");
+  const TabuPlan pl = tabu_assign_plan(L, V);
+  if (pl.lds > TABU_LDS_LIMIT) throw std::invalid_argument("tabu_assign: a chain's tables exceed 64 KiB of LDS");
+  if (P <= 0 || iters == 0) return;
+  const int grid = (P + pl.waves - 1) / pl.waves;
+  if (pl.staged)
+    tabu_assign_kernel<true><<<grid, 64 * pl.waves, pl.lds, stream>>>(cost, L, V, conflict, sol, cur_cost, best_sol,
+                                                                     best_cost, tabu, hist, P, (int)iters,
+                                                                     (int)it_begin, (int)tenure, stats);
+  else
+    tabu_assign_kernel<false><<<grid, 64 * pl.waves, pl.lds, stream>>>(cost, L, V, conflict, sol, cur_cost, best_sol,
+                                                                      best_cost, tabu, hist, P, (int)iters,
+                                                                      (int)it_begin, (int)tenure, stats);
   AV_HIP_CHECK(hipGetLastError());
 }
 

@@ -8,6 +8,7 @@ from .sa import SaDomain, SaRun, sa_chains_init, sa_chains_reference, sa_exp
 from .search import (BayesianOptimizer, EvolutionaryOptimizer, GeneticAlgorithm, OptResult, RandomSearch,
                      SimulatedAnnealing, TabuSearch, local_focussed, local_trajectory, parameter_search, sa_assign,
                      sa_assign_reference)
+from .tabu import TabuRun, tabu_assign_advance, tabu_assign_reference
 
 __all__ = [
     "AssignmentDomain", "CallbackDomain", "FunctionDomain", "SearchDomain", "FeatureSubsetDomain",
@@ -15,5 +16,5 @@ __all__ = [
     "EvolutionaryOptimizer", "GeneticAlgorithm", "OptResult", "RandomSearch", "SimulatedAnnealing", "TabuSearch",
     "local_focussed", "local_trajectory", "parameter_search", "sa_assign", "sa_assign_reference",
     "SaDomain", "SaRun", "sa_chains_init", "sa_chains_reference", "sa_exp", "sa_meeting_reference", "sa_meeting_run",
-    "sa_subset_reference", "sa_subset_run",
+    "sa_subset_reference", "sa_subset_run", "TabuRun", "tabu_assign_advance", "tabu_assign_reference",
 ]

@@ -22,6 +22,11 @@ chain per lane; ``sa_subset_kernel``: 1 to 16 waves per chain over a shared row 
 twins they equal bit for bit, the Metropolis decision included.  So does the island genetic
 algorithm (optimize/ga.py: one workgroup per island, pool / costs / children in LDS, all
 generations of a migration interval per launch; its numpy twin is the CPU path, bit-equal).
+Tabu search over an :class:`AssignmentDomain` on a GPU is one launch of ``tabu_assign_kernel``
+(optimize/tabu.py: one chain per wave; tabu table, blocked counts, solution in LDS; the full
+L x V neighbourhood scored and reduced inside the wave every iteration), bit-equal to its numpy
+twin; the torch path (three [P, L, V] tensors, a validity GEMM and five host reads per iteration)
+stays the CPU default.
 Other domains take batched tensor ops per generation; the GA over them runs one generation per
 ISLAND (each island draws from its own generator, keyed by global island index, so that results do
 not depend on the world size): ~12 small launches per island per generation.  Measured on one
@@ -654,15 +659,68 @@ class TabuSearch:
     single-reassignment neighbourhood ``[P, L, V]`` in closed form (cost delta from the table,
     validity of every move via one ``conflict @ occupancy`` GEMM), masks tabu moves unless they
     beat the best (aspiration), and takes the best admissible move; reversing a move is tabu for
-    ``tenure`` iterations (TabuSearchDomain purge, J/optimize/TabuSearchDomain.java:54-66)."""
+    ``tenure`` iterations (TabuSearchDomain purge, J/optimize/TabuSearchDomain.java:54-66).
+
+    On a GPU the whole run is one launch of ``tabu_assign_kernel`` (optimize/tabu.py: one chain per
+    wave, the tabu table and the blocked counts of every cell in LDS) whenever the tables fit its
+    LDS (:meth:`_chain_engine`); its numpy twin, which it equals bit for bit, runs on the CPU
+    with ``use_kernel=True``.  The torch path above is the CPU default and ``use_kernel=False``."""
 
     def __init__(self, domain: AssignmentDomain, n_chains: int = 8, iters: int = 200, tenure: int = 7, seed: int = 0,
-                 comm: Comm | None = None):
+                 comm: Comm | None = None, use_kernel: bool | None = None):
         self.d, self.P, self.iters, self.tenure, self.seed, self.comm = domain, n_chains, iters, tenure, seed, comm
+        self.use_kernel = use_kernel
+
+    def _chain_engine(self) -> str | None:
+        """``tabu_assign_kernel`` / ``tabu_assign_twin`` when the one-launch engine applies, or None (the
+        generic torch path): an AssignmentDomain whose tables fit the kernel's LDS
+        (``tabu.tabu_assign_lds`` <= 64 KiB, V <= 32767) — on a GPU by default, on the CPU (the
+        twin) only when ``use_kernel`` is True, so CPU default results are unchanged.  Measured on
+        one MI355X against the generic path (profiles/tabu_assign_bench.jsonl, 24 x 10 cells, 200
+        iterations, whole runs): 54 x / 22 x / 6.3 x faster at 16 / 1,024 / 16,384 chains; at 16
+        chains no size up to the LDS limit loses (profiles/tabu_assign_cap_sweep.jsonl: 8.6 x at
+        160 x 48), so the dispatch has no size cap."""
+        from . import tabu as tb
+        d = self.d
+        if self.use_kernel is False or not isinstance(d, AssignmentDomain):
+            return None
+        if not (self.use_kernel is True or d.device.type == "cuda"):
+            return None
+        if d.V > 32767 or tb.tabu_assign_lds(d.L, d.V) > tb.LDS_LIMIT or self.iters + self.tenure >= 2 ** 31:
+            return None
+        return "tabu_assign_kernel" if d.device.type == "cuda" else "tabu_assign_twin"
+
+    def _run_kernel(self, comm, engine: str) -> OptResult:
+        """Chains are GLOBAL: rank ``r`` runs chains ``[r n, (r + 1) n)`` of one population of ``W n``
+        start solutions drawn from the seed alone, so the W-rank run equals one process with
+        ``W n`` chains.  The population is drawn and priced whole on the host, then cut: both
+        devices and every world size start from the same bits (a torch reduction may round
+        differently for another batch shape)."""
+        from .tabu import TabuRun, tabu_assign_advance
+        d, n = self.d, self.P
+        W, r = comm.world, comm.rank
+        host = d if d.device.type == "cpu" else d.to("cpu")
+        pop = sa_assign_init(host, W * n, self.seed, 0, total=W * n)
+        sol, cost = pop[r * n:(r + 1) * n], host.evaluate(pop)[r * n:(r + 1) * n]
+        run = TabuRun(self.iters, self.tenure, 0, r * n)
+        best, bc, stats, _, _, _, hist = tabu_assign_advance(d, sol.to(d.device), cost.to(d.device), run, d.device)
+        best, bc, hist = (torch.as_tensor(x) for x in (best, bc, hist))
+        if comm.is_distributed:
+            v = torch.tensor([stats[k] for k in ("moves", "stalls", "aspirated")], dtype=torch.float64)
+            comm.all_reduce(v)
+            stats = dict(zip(("moves", "stalls", "aspirated"), (int(x) for x in v.tolist())))
+        ha = comm.all_gather_v(hist.cpu().contiguous()) if comm.is_distributed else hist
+        history = ha.min(0).values.tolist() if ha.shape[0] else []
+        best, bc = best.long().to(d.device), bc.to(d.device)
+        b, c = _global_best(comm, bc, best)
+        return OptResult(b, c, bc, best, history, {**stats, "engine": engine})
 
     def run(self) -> OptResult:
         comm = self.comm or get_comm()
         d = self.d
+        engine = self._chain_engine()
+        if engine is not None:
+            return self._run_kernel(comm, engine)
         dev, L, V, P = d.device, d.L, d.V, self.P
         gen = _gen(dev, self.seed + 15485863 * comm.rank)
         sol, _ = d.random(P, gen)
