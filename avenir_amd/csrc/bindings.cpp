@@ -1761,6 +1761,137 @@ void tabu_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& confli
                    reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), cur_stream(cost));
 }
 
+// The checks shared by the evolutionary bindings (optim.hip::eo_assign_kernel, eo_meeting_kernel):
+// the islands' resumable state pop int16 [I, P, L], pop_cost [I, P], born int32 [I, P], best int16
+// [I, L], best_cost [I], hist [I, iters] and stats int64 [4] on one device, the pool limits and the
+// counter bound.  Returns I, P and the run.
+static std::tuple<int64_t, int64_t, avk::EoRun> eo_check(const char* who, int64_t L, const at::Tensor& pop,
+                                                         const at::Tensor& pop_cost, const at::Tensor& born,
+                                                         const at::Tensor& best, const at::Tensor& best_cost,
+                                                         const at::Tensor& hist, const at::Tensor& stats, int64_t iters,
+                                                         int64_t select, double w, double age_scale, int64_t seed,
+                                                         int64_t it_begin, int64_t island_base) {
+  for (const at::Tensor* t : {&pop, &best}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kShort);
+    TORCH_CHECK(t->is_contiguous(), who, ": pop and best must be contiguous");
+  }
+  TORCH_CHECK(pop.dim() == 3 && pop.size(2) == L, who, ": pop must be [I, P, ", L, "]");
+  const int64_t I = pop.size(0), P = pop.size(1);
+  TORCH_CHECK(I < (1LL << 31), who, ": fewer than 2^31 islands");
+  TORCH_CHECK(P >= 2 && P <= 64, who, ": 2 <= P <= 64");
+  TORCH_CHECK(select >= 1 && select <= P, who, ": 1 <= select <= P");
+  TORCH_CHECK(best.dim() == 2 && best.size(0) == I && best.size(1) == L, who, ": best must be [I, ", L, "]");
+  for (const at::Tensor* t : {&pop_cost, &best_cost, &hist}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kFloat);
+    TORCH_CHECK(t->is_contiguous(), who, ": cost tensors must be contiguous");
+  }
+  TORCH_CHECK(pop_cost.dim() == 2 && pop_cost.size(0) == I && pop_cost.size(1) == P, who, ": pop_cost must be [I, P]");
+  TORCH_CHECK(best_cost.dim() == 1 && best_cost.numel() == I, who, ": best_cost must be [I]");
+  CHECK_DEV(born);
+  CHECK_DTYPE(born, at::kInt);
+  TORCH_CHECK(born.is_contiguous() && born.dim() == 2 && born.size(0) == I && born.size(1) == P, who,
+              ": born must be contiguous int32 [I, P]");
+  TORCH_CHECK(iters >= 0 && it_begin >= 0 && iters < (1LL << 31) && it_begin < (1LL << 31) &&
+              it_begin + iters + P < (1LL << 31), who, ": 0 <= iters, it_begin and it_begin + iters + P < 2^31");
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) == I && hist.size(1) == iters, who, ": hist must be [I, iters]");
+  TORCH_CHECK(island_base >= 0 && island_base < (1LL << 62), who, ": 0 <= island_base < 2^62");
+  TORCH_CHECK(w >= 0.0 && w <= 1.0 && age_scale >= 0.0 && std::isfinite(age_scale), who,
+              ": 0 <= w <= 1 and 0 <= age_scale < inf");
+  CHECK_DEV(stats);
+  CHECK_DTYPE(stats, at::kLong);
+  TORCH_CHECK(stats.is_contiguous() && stats.numel() == 4, who, ": stats must hold 4 entries");
+  for (const at::Tensor* t : {&pop_cost, &born, &best, &best_cost, &hist, &stats})
+    TORCH_CHECK(t->device() == pop.device(), who, ": tensors on one device");
+  return {I, P, avk::EoRun{(long long)iters, (int)select, (float)w, (float)age_scale, (unsigned long long)seed,
+                           (long long)it_begin, (long long)island_base}};
+}
+
+// cost [L, V], conflict [L, L] uint8 or None (the kernel reads its upper triangle).  The kernel
+// indexes the cost table with solution values, so they are checked here once per call.
+void eo_assign(const at::Tensor& cost, const c10::optional<at::Tensor>& conflict, bool swap, at::Tensor& pop,
+               at::Tensor& pop_cost, at::Tensor& born, at::Tensor& best, at::Tensor& best_cost, at::Tensor& hist,
+               int64_t iters, int64_t select, double w, double age_scale, int64_t seed, int64_t it_begin,
+               int64_t island_base, at::Tensor& stats) {
+  CHECK_DEV(cost);
+  CHECK_DTYPE(cost, at::kFloat);
+  TORCH_CHECK(cost.dim() == 2 && cost.size(0) >= 1 && cost.size(0) < (1LL << 20) && cost.size(1) >= 2 &&
+                  cost.size(1) <= 32767 && cost.is_contiguous(),
+              "eo_assign: cost must be contiguous [1 <= L < 2^20, 2 <= V <= 32767]");
+  const int64_t L = cost.size(0), V = cost.size(1);
+  const auto [I, P, run] = eo_check("eo_assign", L, pop, pop_cost, born, best, best_cost, hist, stats, iters, select, w,
+                                    age_scale, seed, it_begin, island_base);
+  TORCH_CHECK(pop.device() == cost.device(), "eo_assign: tensors on one device");
+  const uint8_t* cf = nullptr;
+  if (conflict.has_value() && conflict->defined()) {
+    CHECK_DEV((*conflict));
+    CHECK_DTYPE((*conflict), at::kByte);
+    TORCH_CHECK(conflict->dim() == 2 && conflict->size(0) == L && conflict->size(1) == L && conflict->is_contiguous() &&
+                    conflict->device() == cost.device(), "eo_assign: conflict must be contiguous [L, L] on the device of cost");
+    cf = conflict->data_ptr<uint8_t>();
+  }
+  const avk::EoPlan pl = avk::eo_assign_plan((int)P, (int)L);
+  TORCH_CHECK(pl.islands >= 1, "eo_assign: one island's pool (", pl.lds, " bytes) exceeds 64 KiB of LDS");
+  for (const at::Tensor* t : {&pop, &best})
+    if (t->numel())
+      TORCH_CHECK(t->min().item<int>() >= 0 && t->max().item<int>() < V, "eo_assign: solution values must lie in [0, V)");
+  if (I == 0 || iters == 0) return;
+  DevGuard g(cost.device());
+  avk::eo_assign(cost.data_ptr<float>(), (int)L, (int)V, cf, swap ? 1 : 0, pop.data_ptr<int16_t>(),
+                 pop_cost.data_ptr<float>(), born.data_ptr<int>(), best.data_ptr<int16_t>(), best_cost.data_ptr<float>(),
+                 hist.data_ptr<float>(), reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), (int)I, (int)P,
+                 run, cur_stream(cost));
+}
+
+void eo_meeting(const at::Tensor& days, const at::Tensor& hours, const at::Tensor& minutes, const at::Tensor& dur,
+                const at::Tensor& share, const at::Tensor& member, const at::Tensor& role_w, const at::Tensor& blocked,
+                const at::Tensor& ordered, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& born, at::Tensor& best,
+                at::Tensor& best_cost, at::Tensor& hist, int64_t iters, int64_t select, double w, double age_scale,
+                int64_t seed, int64_t it_begin, int64_t island_base, at::Tensor& stats) {
+  const avk::GaMeetingDomain dom =
+      meeting_domain("eo_meeting", days, hours, minutes, dur, share, member, role_w, blocked, ordered);
+  const auto [I, P, run] = eo_check("eo_meeting", 3 * (int64_t)dom.M, pop, pop_cost, born, best, best_cost, hist, stats,
+                                    iters, select, w, age_scale, seed, it_begin, island_base);
+  TORCH_CHECK(pop.device() == days.device(), "eo_meeting: tensors on one device");
+  const avk::EoPlan pl = avk::eo_meeting_plan((int)P, dom.M);
+  TORCH_CHECK(pl.islands >= 1, "eo_meeting: one island's pool (", pl.lds, " bytes) exceeds 64 KiB of LDS");
+  meeting_indices(dom, pop);
+  meeting_indices(dom, best);
+  if (I == 0 || iters == 0) return;
+  DevGuard g(pop.device());
+  avk::eo_meeting(dom, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(), born.data_ptr<int>(),
+                  best.data_ptr<int16_t>(), best_cost.data_ptr<float>(), hist.data_ptr<float>(),
+                  reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), (int)I, (int)P, run, cur_stream(pop));
+}
+
+// waves_per_island: 0 lets the launcher choose; 1, 2, 4, 8 or 16 forces it (no result depends on it)
+void eo_subset(const at::Tensor& LL, const at::Tensor& log_prior, const at::Tensor& labels, int64_t min_size,
+               int64_t max_size, at::Tensor& pop, at::Tensor& pop_cost, at::Tensor& born, at::Tensor& best,
+               at::Tensor& best_cost, at::Tensor& hist, int64_t iters, int64_t select, double w, double age_scale,
+               int64_t seed, int64_t it_begin, int64_t island_base, at::Tensor& stats, int64_t waves_per_island) {
+  subset_check(LL, log_prior, labels, "eo_subset");
+  const int64_t N = LL.size(0), F = LL.size(1), C = LL.size(2);
+  TORCH_CHECK(min_size >= 0 && min_size <= max_size && max_size <= 32, "eo_subset: 0 <= min_size <= max_size <= 32");
+  TORCH_CHECK(waves_per_island == 0 || waves_per_island == 1 || waves_per_island == 2 || waves_per_island == 4 ||
+              waves_per_island == 8 || waves_per_island == 16, "eo_subset: waves_per_island must be 0, 1, 2, 4, 8 or 16");
+  const auto [I, P, run] = eo_check("eo_subset", F, pop, pop_cost, born, best, best_cost, hist, stats, iters, select, w,
+                                    age_scale, seed, it_begin, island_base);
+  TORCH_CHECK(pop.device() == LL.device(), "eo_subset: tensors on one device");
+  TORCH_CHECK(avk::sa_subset_plan((int)N, (int)F, (int)C, (int)std::max<int64_t>(I, 1), (int)waves_per_island).lds <=
+                  56 * 1024, "eo_subset: the row tile exceeds its LDS");
+  for (const at::Tensor* t : {&pop, &best})
+    if (t->numel())
+      TORCH_CHECK(t->min().item<int>() >= 0 && t->max().item<int>() <= 1, "eo_subset: masks must be 0 or 1");
+  if (I == 0 || iters == 0) return;
+  DevGuard g(LL.device());
+  avk::eo_subset(LL.data_ptr<float>(), log_prior.data_ptr<float>(), labels.data_ptr<int>(), (int)N, (int)F, (int)C,
+                 (int)min_size, (int)max_size, pop.data_ptr<int16_t>(), pop_cost.data_ptr<float>(), born.data_ptr<int>(),
+                 best.data_ptr<int16_t>(), best_cost.data_ptr<float>(), hist.data_ptr<float>(),
+                 reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()), (int)I, (int)P, run,
+                 (int)waves_per_island, cur_stream(LL));
+}
+
 // ---------------------------------------------------------------------------------------------
 // generalised linear models (K13)
 // ---------------------------------------------------------------------------------------------
@@ -4590,6 +4721,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("ga_subset", &ga_subset);
   m.def("tabu_assign", &tabu_assign);
   m.def("tabu_assign_lds", [](int64_t L, int64_t V) { return (int64_t)avk::tabu_assign_lds((int)L, (int)V); });
+  m.def("eo_assign", &eo_assign);
+  m.def("eo_meeting", &eo_meeting);
+  m.def("eo_subset", &eo_subset);
+  // (islands per wave, LDS bytes) of the evolutionary launchers; 0 islands = no kernel
+  m.def("eo_assign_plan", [](int64_t P, int64_t L) {
+    const avk::EoPlan pl = avk::eo_assign_plan((int)P, (int)L);
+    return std::make_pair((int64_t)pl.islands, (int64_t)pl.lds);
+  });
+  m.def("eo_meeting_plan", [](int64_t P, int64_t M) {
+    const avk::EoPlan pl = avk::eo_meeting_plan((int)P, (int)M);
+    return std::make_pair((int64_t)pl.islands, (int64_t)pl.lds);
+  });
   m.def("sa_meeting", &sa_meeting);
   m.def("sa_meeting_lds", [](int64_t M) { return (int64_t)avk::sa_meeting_lds((int)M); });
   m.def("sa_subset", &sa_subset);

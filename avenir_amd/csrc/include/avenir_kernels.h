@@ -197,6 +197,37 @@ size_t tabu_assign_lds(int L, int V);
 void tabu_assign(const float* cost, int L, int V, const uint8_t* conflict, short* sol, float* cur_cost,
                  short* best_sol, float* best_cost, int* tabu, float* hist, int P, long long iters, long long it_begin,
                  long long tenure, unsigned long long* stats, hipStream_t stream);
+// Evolutionary optimiser (steady-state islands: tournament, mutated clone, purge by cost and age; one
+// launch, resumable; one island per lane): pop int16 [I][P][L], pop_cost [I][P], born int32 [I][P]
+// (distinct insertion stamps, a fresh pool has born[j] = j), best int16 [I][L] and best_cost [I] in
+// and out, hist [I][iters] = the best cost after every iteration, stats[0..2] += inserted, stalls,
+// improved.  Row i is global island island_base + i; iterations [it_begin, it_begin + iters) with
+// it_begin + iters + P < 2^31; 2 <= P <= 64, 1 <= select <= P, 0 <= w <= 1; every pop / best value
+// inside its table.
+struct EoRun {
+  long long iters;
+  int select;
+  float w, age_scale;  // purge: w cost + (1 - w) age, age scaled by age_scale
+  unsigned long long seed;
+  long long it_begin, island_base;
+};
+constexpr size_t EO_LDS_LIMIT = 64 * 1024;
+struct EoPlan {
+  int islands;  // islands per wave: the largest of 64, 32, ..., 1 that fits; 0 = no kernel
+  size_t lds;   // bytes of dynamic LDS per workgroup (with islands = 0: what one island would take)
+};
+EoPlan eo_assign_plan(int P, int L);
+EoPlan eo_meeting_plan(int P, int M);
+void eo_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* pop, float* pop_cost,
+               int* born, short* best, float* best_cost, float* hist, unsigned long long* stats, int I, int P,
+               const EoRun& run, hipStream_t stream);
+void eo_meeting(const GaMeetingDomain& dom, short* pop, float* pop_cost, int* born, short* best, float* best_cost,
+                float* hist, unsigned long long* stats, int I, int P, const EoRun& run, hipStream_t stream);
+// feature subsets: pop [I][P][F] and best [I][F] of 0 / 1; islands of waves_per_island = 1, 2, 4, 8 or 16
+// waves over a shared row tile (0: the launcher's choice; sa_subset_plan; no result depends on it)
+void eo_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, short* pop, float* pop_cost, int* born, short* best, float* best_cost, float* hist,
+               unsigned long long* stats, int I, int P, const EoRun& run, int waves_per_island, hipStream_t stream);
 
 // ---- linear.hip (K13) ----------------------------------------------------------------------
 int glm_grid(long long n);

@@ -1,7 +1,8 @@
 // K22: stochastic search in persistent launches (CDNA4, gfx950) — island genetic algorithms and
 // simulated-annealing chains over three domains each: assignments (a [L][V] cost table and an
-// [L][L] conflict table), meeting schedules and feature subsets scored by naive Bayes; and tabu
-// search over assignments (tabu_assign_kernel, one chain per wave, at the end of the kernels).
+// [L][L] conflict table), meeting schedules and feature subsets scored by naive Bayes; tabu
+// search over assignments (tabu_assign_kernel, one chain per wave); and the evolutionary optimiser's
+// steady-state islands over the same three domains (eo_*_kernel on the frame eo_island, at the end).
 //
 // Reference: one SA chain or one GA per Spark partition, mutating string-encoded solutions through
 // the BasicSearchDomain SPI (S/optimize/SimulatedAnnealing.scala:111-187,
@@ -13,6 +14,7 @@
 #include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "avenir_common.h"
 #include "avenir_kernels.h"
@@ -224,19 +226,22 @@ __device__ __forceinline__ void ga_island(GaPool<T>& V, const GaArgs& A, int L, 
 //   * invalid: two conflicting positions share a value;
 //   * cost: fp32 sum of C[l][s_l] in position order times 1/L.
 // optimize/ga.py::ga_assign_reference is the bit-exact host twin.
+// S is the element stride of s: 1 for rows, IW for the lane-private columns of the evolutionary kernels.
+template <int S = 1>
 __device__ __forceinline__ bool ga_valid(const short* s, int L, const uint8_t* __restrict__ conflict) {
   if (conflict)
     for (int i = 0; i < L; ++i)
       for (int j = i + 1; j < L; ++j)
-        if (s[i] == s[j] && conflict[(long long)i * L + j]) return false;
+        if (s[i * S] == s[j * S] && conflict[(long long)i * L + j]) return false;
   return true;
 }
 
+template <int S = 1>
 __device__ __forceinline__ float ga_price(const short* s, int L, int V, const float* __restrict__ cost,
                                           const uint8_t* __restrict__ conflict, float invL, float invalid) {
   float acc = 0.f;
-  for (int l = 0; l < L; ++l) acc += cost[(long long)l * V + s[l]];
-  return ga_valid(s, L, conflict) ? acc * invL : invalid;
+  for (int l = 0; l < L; ++l) acc += cost[(long long)l * V + s[l * S]];
+  return ga_valid<S>(s, L, conflict) ? acc * invL : invalid;
 }
 
 __global__ __launch_bounds__(64) void ga_assign_kernel(
@@ -1256,6 +1261,461 @@ __global__ __launch_bounds__(256) void tabu_assign_kernel(
   }
 }
 
+// ---- evolutionary optimiser: steady-state islands, one island per lane ---------------------------
+// Reference: EvolutionaryOptimizer (P/mlextra/optpopu.py:32-92): tournament selection, a mutated
+// clone, purge by cost and age.  An island's state is its pool pop int16 [P][L], the members' costs
+// fp32 [P] and insertion stamps born int32 [P] (distinct; a fresh pool has born[j] = j), the best
+// solution seen and its cost.  Island g = island_base + i is GLOBAL; iteration `it` of
+// [it_begin, it_begin + iters), every fp32 operation rounded on its own:
+//   1. tournament: k = select distinct slots.  Draw j = 0..k-1 takes
+//      t = min((int)(u_j (float)(P - j)), P - j - 1) and picks the t-th slot, slots ascending, that
+//      no earlier draw picked; u_j is word j & 3 of Philox(seed ^ EO_SEL_KEY, 16 it + (j >> 2), g).
+//      The picked set is a 64-bit mask in registers.  The winner is the picked slot of smallest
+//      cost, ties to the earlier draw;
+//   2. clone and mutate: attempt t = 0..EO_MAX_TRY-1 draws Philox(seed ^ GA_MUT_KEY, 16 it + t, g),
+//      word x the position, word y the value, and applies the domain's mutation (that of its island
+//      GA kernel) to the clone of the winner; an attempt that leaves the whole clone invalid is
+//      taken back, the first valid attempt is the child.  Without one the iteration inserts
+//      nothing and counts in `stalls`;
+//   3. the child is priced from scratch by the domain's price function;
+//   4. purge: a_j = the number of members with an older stamp than member j,
+//      age_j = ((float)(P - a_j) age_scale) / (float)P, fin_j = cost_j when finite, else 1e30,
+//      aggr_j = w fin_j + (1 - w) age_j; the victim has the largest aggr, ties to the oldest.  The
+//      child takes the victim's slot with stamp P + it (`inserted`);
+//   5. a child cost strictly below best_cost replaces the best (`improved`);
+//      hist[i][it - it_begin] = the island's best cost after the iteration.
+// 2 <= P <= 64, 1 <= select <= P, it_begin + iters + P < 2^31.  A run cut into segments through
+// the state equals one run.  optimize/eo.py::eo_islands_reference is the frame's bit-exact host twin.
+//
+// Assignments and meetings (eo_assign_kernel, eo_meeting_kernel; subsets: eo_subset_kernel below):
+// one island per lane, one wave per workgroup carrying IW islands: the pool, the clone, the costs
+// and the age ranks a_j are columns `lane` of [.][IW] LDS tiles (lane-private; no private array is
+// indexed at run time).  IW is the largest of 64, 32, ..., 1 whose columns fit 64 KiB
+// (avk::eo_assign_plan / eo_meeting_plan): big pools leave lanes idle.  The ranks are kept
+// incrementally (an insert lowers the ranks above the victim's by one, the child gets P - 1), so an
+// iteration scans the pool once for the tournament and once for the purge; stamps are only read
+// at the start and written to global memory at an insert, as is the best solution at an improvement.
+constexpr int EO_MAX_TRY = 5;  // the reference's maxTry
+constexpr unsigned long long EO_SEL_KEY = 0xA0761D6478BD642Full;
+
+struct EoArgs {
+  int I, P, iters, select, it_begin;
+  float w, age_scale;
+  unsigned long long seed;
+  long long island_base;
+};
+
+struct EoIsland {  // what an island carries besides its pool
+  float bc;
+  unsigned long long inserted, stalls, improved;
+};
+
+// position of the t-th (from 0) set bit of m, which has more than t set bits
+__device__ __forceinline__ int eo_nth_set(unsigned long long m, int t) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w; w >>= 1) {
+    const int c = __popcll(m & ((1ull << w) - 1ull));
+    if (t >= c) {
+      t -= c;
+      m >>= w;
+      pos += w;
+    }
+  }
+  return pos;
+}
+
+// Step 4's score of a member of cost c and age rank a, each operation rounded on its own
+__device__ __forceinline__ float eo_aggr(const EoArgs& A, float c, int a) {
+#pragma clang fp contract(off)
+  const float fin = isfinite(c) ? c : 1e30f;
+  const float num = (float)(A.P - a) * A.age_scale;
+  const float age = num / (float)A.P;
+  const float x = A.w * fin, y = (1.f - A.w) * age;
+  return x + y;
+}
+
+// a_j of member j from the island's stamps
+__device__ __forceinline__ int eo_rank(const int* __restrict__ gborn, int P, int j) {
+  const int bj = gborn[j];
+  int a = 0;
+  for (int i = 0; i < P; ++i) a += gborn[i] < bj;
+  return a;
+}
+
+// A pool whose costs pc[j * IW] and age ranks rk[j * IW] are lane-private LDS columns (the island of
+// a lane): the purge is two scans of the P members.
+template <int IW>
+struct EoColumns {
+  float* pc;
+  short* rk;
+  int* gborn;  // the island's row of born
+  __device__ __forceinline__ void init(const EoArgs& A) {
+    for (int j = 0; j < A.P; ++j) rk[j * IW] = (short)eo_rank(gborn, A.P, j);
+  }
+  __device__ __forceinline__ float cost(int slot) const { return pc[slot * IW]; }
+  // the child of cost cc replaces the victim; returns the victim's slot
+  __device__ __forceinline__ int purge(const EoArgs& A, float cc, int it) {
+    const int P = A.P;
+    int vic = 0, vr = 0;
+    float va = 0.f;
+    for (int j = 0; j < P; ++j) {
+      const int a = rk[j * IW];
+      const float aggr = eo_aggr(A, pc[j * IW], a);
+      if (j == 0 || aggr > va || (aggr == va && a < vr)) {
+        va = aggr;
+        vr = a;
+        vic = j;
+      }
+    }
+    for (int j = 0; j < P; ++j) {
+      const int a = rk[j * IW];
+      if (a > vr) rk[j * IW] = (short)(a - 1);
+    }
+    rk[vic * IW] = (short)(P - 1);
+    pc[vic * IW] = cc;
+    gborn[vic] = P + it;
+    return vic;
+  }
+};
+
+// The iterations of one island.  `pool` holds the members' costs and age ranks (EoColumns, EoLanes):
+// cost(slot), and purge(A, cc, it) -> the victim's slot.  clone(j): member j -> the clone;
+// mutate(x, y): one attempt on the clone; valid(): is the clone valid now; undo(): take the attempt
+// back; price(ok) -> the clone's cost: every thread calls it every iteration (it may hold
+// barriers), its value counts only where ok; insert(j): the clone -> slot j; improved(): the clone
+// is the new best.  An island that is not `live` only keeps price's barriers; `lead` marks the one
+// thread of an island that writes its row ghist of hist.
+template <class Pool, class Clone, class Mutate, class Valid, class Undo, class Price, class Insert, class Improved>
+__device__ __forceinline__ void eo_island(const EoArgs& A, unsigned long long g, bool live, bool lead, EoIsland& S,
+                                          Pool& pool, float* __restrict__ ghist, Clone clone, Mutate mutate,
+                                          Valid valid, Undo undo, Price price, Insert insert, Improved improved) {
+  const int P = A.P;
+  const unsigned long long all = P == 64 ? ~0ull : (1ull << P) - 1ull;
+  for (int k = 0; k < A.iters; ++k) {
+    const int it = A.it_begin + k;
+    bool ok = false;
+    if (live) {
+      // 1. tournament
+      unsigned long long free = all;
+      av::u4 R{0, 0, 0, 0};
+      int win = 0;
+      float wc = 0.f;
+      for (int j = 0; j < A.select; ++j) {
+        const int q = j & 3;
+        if (q == 0)
+          R = av::philox_draw(A.seed ^ EO_SEL_KEY, 16ull * (unsigned long long)it + (unsigned long long)(j >> 2), g);
+        const unsigned word = q == 0 ? R.x : q == 1 ? R.y : q == 2 ? R.z : R.w;
+        const int n = P - j;
+        const int t = min((int)(av::u32_to_unit(word) * (float)n), n - 1);
+        const int slot = eo_nth_set(free, t);
+        free &= ~(1ull << slot);
+        const float c = pool.cost(slot);
+        if (j == 0 || c < wc) {
+          wc = c;
+          win = slot;
+        }
+      }
+      // 2. clone and mutate
+      clone(win);
+      for (int t = 0; t < EO_MAX_TRY && !ok; ++t) {
+        const av::u4 Q = av::philox_draw(A.seed ^ GA_MUT_KEY, 16ull * (unsigned long long)it + (unsigned long long)t, g);
+        mutate(Q.x, Q.y);
+        ok = valid();
+        if (!ok) undo();
+      }
+    }
+    // 3. price
+    const float cc = price(ok);
+    if (ok) {
+      // 4. purge
+      insert(pool.purge(A, cc, it));
+      ++S.inserted;
+      // 5. best
+      if (cc < S.bc) {
+        S.bc = cc;
+        improved();
+        ++S.improved;
+      }
+    } else if (live) {
+      ++S.stalls;
+    }
+    if (lead) ghist[k] = S.bc;
+  }
+}
+
+__device__ __forceinline__ void eo_report(unsigned long long* __restrict__ stats, const EoIsland& S) {
+  if (S.inserted) atomicAdd(&stats[0], S.inserted);
+  if (S.stalls) atomicAdd(&stats[1], S.stalls);
+  if (S.improved) atomicAdd(&stats[2], S.improved);
+}
+
+// bytes of the lane-private columns of one island: costs, (meetings: start seconds and day bits,)
+// age ranks, pool and clone — the 4-byte arrays first, so every array is aligned at any IW
+__host__ __device__ constexpr size_t eo_island_bytes(size_t P, size_t L, size_t M) {
+  return 4 * P + 8 * M + 2 * P + 2 * P * L + 2 * L;
+}
+
+// Assignments: the mutation of ga_assign_kernel (one position to a different value; with `swap` the
+// first other position holding that value takes the old one), ga_valid and ga_price on the clone's
+// column.  A child is valid when it is priced, so ga_price runs without the conflict table.
+template <int IW>
+__global__ __launch_bounds__(64) void eo_assign_kernel(
+    const float* __restrict__ cost, int L, int V, const uint8_t* __restrict__ conflict, int swap,
+    short* __restrict__ pop, float* __restrict__ pop_cost, int* __restrict__ born, short* __restrict__ best,
+    float* __restrict__ best_cost, float* __restrict__ hist, unsigned long long* __restrict__ stats, EoArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char eo_lds[];
+  const int lane = threadIdx.x, P = A.P;
+  const long long i = (long long)blockIdx.x * IW + lane;
+  if (lane >= IW || i >= A.I) return;
+  float* pc = reinterpret_cast<float*>(eo_lds) + lane;                    // cost of member j at pc[j * IW]
+  short* rk = reinterpret_cast<short*>(eo_lds + (size_t)4 * P * IW) + lane;
+  short* pl = rk + (size_t)P * IW;                                        // element l of member j at pl[(j L + l) IW]
+  short* c = pl + (size_t)P * L * IW;                                     // the clone
+  short* gpop = pop + i * P * L;
+  short* gbest = best + i * L;
+  for (int e = 0; e < P * L; ++e) pl[e * IW] = gpop[e];
+  for (int j = 0; j < P; ++j) pc[j * IW] = pop_cost[i * P + j];
+  EoIsland S{best_cost[i], 0, 0, 0};
+  const float invL = 1.f / (float)L;
+  int pos = 0, old = 0, v = 0, holder = -1;
+  EoColumns<IW> pool{pc, rk, born + i * P};
+  pool.init(A);
+  eo_island(
+      A, (unsigned long long)(A.island_base + i), true, true, S, pool, hist + i * A.iters,
+      [&](int j) {
+        for (int l = 0; l < L; ++l) c[l * IW] = pl[(j * L + l) * IW];
+      },
+      [&](unsigned qp, unsigned qv) {
+        pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+        old = c[pos * IW];
+        v = min((int)(av::u32_to_unit(qv) * (float)(V - 1)), V - 2);
+        v += v >= old;
+        holder = -1;
+        if (swap)
+          for (int j = 0; j < L; ++j)
+            if (j != pos && c[j * IW] == v) { holder = j; break; }
+        if (holder >= 0) c[holder * IW] = (short)old;
+        c[pos * IW] = (short)v;
+      },
+      [&] { return ga_valid<IW>(c, L, conflict); },
+      [&] {
+        c[pos * IW] = (short)old;
+        if (holder >= 0) c[holder * IW] = (short)v;
+      },
+      [&](bool ok) { return ok ? ga_price<IW>(c, L, V, cost, nullptr, invL, 0.f) : 0.f; },
+      [&](int j) {
+        for (int l = 0; l < L; ++l) pl[(j * L + l) * IW] = c[l * IW];
+      },
+      [&] {
+        for (int l = 0; l < L; ++l) gbest[l] = c[l * IW];
+      });
+  for (int e = 0; e < P * L; ++e) gpop[e] = pl[e * IW];
+  for (int j = 0; j < P; ++j) pop_cost[i * P + j] = pc[j * IW];
+  best_cost[i] = S.bc;
+  eo_report(stats, S);
+}
+
+// Meeting schedules: the mutation of ga_meeting_kernel (one index to a different value of its table,
+// a one-value table leaves the clone alone), mt_valid and mt_cost on the clone's start seconds and
+// day bits, two more lane-private columns; the domain is staged in front of the columns.
+template <int IW>
+__global__ __launch_bounds__(64) void eo_meeting_kernel(
+    avk::GaMeetingDomain dom, short* __restrict__ pop, float* __restrict__ pop_cost, int* __restrict__ born,
+    short* __restrict__ best, float* __restrict__ best_cost, float* __restrict__ hist,
+    unsigned long long* __restrict__ stats, EoArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char eo_lds[];
+  const int lane = threadIdx.x, P = A.P, M = dom.M, L = 3 * M;
+  const MtLds D = mt_stage(dom, reinterpret_cast<int*>(eo_lds), lane);
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * IW + lane;
+  if (lane >= IW || i >= A.I) return;
+  unsigned char* at = eo_lds + (size_t)MT_DOM_INTS * sizeof(int);
+  float* pc = reinterpret_cast<float*>(at) + lane;                        at += (size_t)4 * P * IW;
+  int* st = reinterpret_cast<int*>(at) + lane;                            at += (size_t)4 * M * IW;
+  unsigned* db = reinterpret_cast<unsigned*>(at) + lane;                  at += (size_t)4 * M * IW;
+  short* rk = reinterpret_cast<short*>(at) + lane;
+  short* pl = rk + (size_t)P * IW;
+  short* c = pl + (size_t)P * L * IW;
+  short* gpop = pop + i * P * L;
+  short* gbest = best + i * L;
+  for (int e = 0; e < P * L; ++e) pl[e * IW] = gpop[e];
+  for (int j = 0; j < P; ++j) pc[j * IW] = pop_cost[i * P + j];
+  EoIsland S{best_cost[i], 0, 0, 0};
+  int pos = 0, mi = 0, card = 0, old = 0;
+  auto put = [&](int v) {
+    if (card > 1) {
+      c[pos * IW] = (short)v;
+      mt_place<IW>(D, c, mi, st, db);
+    }
+  };
+  EoColumns<IW> pool{pc, rk, born + i * P};
+  pool.init(A);
+  eo_island(
+      A, (unsigned long long)(A.island_base + i), true, true, S, pool, hist + i * A.iters,
+      [&](int j) {
+        for (int l = 0; l < L; ++l) c[l * IW] = pl[(j * L + l) * IW];
+        for (int m = 0; m < M; ++m) mt_place<IW>(D, c, m, st, db);
+      },
+      [&](unsigned qp, unsigned qv) {
+        pos = min((int)(av::u32_to_unit(qp) * (float)L), L - 1);
+        mi = pos / 3;
+        const int comp = pos - 3 * mi;
+        card = comp == 0 ? dom.nd : comp == 1 ? dom.nh : dom.nm;
+        old = c[pos * IW];
+        int v = min((int)(av::u32_to_unit(qv) * (float)(card - 1)), card - 2);
+        v += v >= old;
+        put(v);
+      },
+      [&] { return mt_valid<IW>(D, st); },
+      [&] { put(old); },
+      [&](bool ok) { return ok ? mt_cost<IW>(D, db) : 0.f; },
+      [&](int j) {
+        for (int l = 0; l < L; ++l) pl[(j * L + l) * IW] = c[l * IW];
+      },
+      [&] {
+        for (int l = 0; l < L; ++l) gbest[l] = c[l * IW];
+      });
+  for (int e = 0; e < P * L; ++e) gpop[e] = pl[e * IW];
+  for (int j = 0; j < P; ++j) pop_cost[i * P + j] = pc[j * IW];
+  best_cost[i] = S.bc;
+  eo_report(stats, S);
+}
+
+// A pool held by a wave, one member per lane (lane j < P: mask, cost and age rank in registers).
+// Every lane of the wave follows the same island, so slots and costs are wave-uniform: a member's
+// cost is one v_readlane, and the victim is the wave minimum of an order-preserving 64-bit key —
+// the complement of aggr's key above the rank and the lane, so the largest aggr wins, ties to the
+// oldest.  All 64 lanes must be active in purge.
+struct EoLanes {
+  unsigned mk;
+  float c;
+  int a, lane;
+  int* gborn;  // the island's row of born; written by the island's leading wave
+  bool writer;
+  __device__ __forceinline__ float cost(int slot) const {
+    return av::lane_f(c, __builtin_amdgcn_readfirstlane(slot));
+  }
+  __device__ __forceinline__ int purge(const EoArgs& A, float cc, int it) {
+    unsigned long long key = TB_NONE;
+    if (lane < A.P)
+      key = ((unsigned long long)(~tb_key(eo_aggr(A, c, a))) << 32) | ((unsigned)a << 8) | (unsigned)lane;
+    key = tb_wave_min(key);
+    const int vic = (int)(key & 0xffu), vr = (int)((key >> 8) & 0xffffffu);
+    if (a > vr) --a;
+    if (lane == vic) {
+      a = A.P - 1;
+      c = cc;
+      if (writer) gborn[vic] = A.P + it;
+    }
+    return vic;
+  }
+};
+
+// Feature subsets: the structure of sa_subset_kernel — workgroups of 256 or 1,024 threads whose waves
+// are split into islands of w = 1..16 waves over one shared staged row tile, the clone's mask in a
+// scalar register, ballot counts meeting in the three-deep integer LDS counter (one barrier per tile
+// and iteration).  The pool is an EoLanes in every wave of the island: all of them draw the same
+// Philox words and see the same counts, so the copies stay equal without LDS or a further barrier.
+// A mutation flips one bit (the value word is unused); valid: min_size <= popcount <= max_size;
+// cost = (float)errors / (float)N.  pop, best stay int16 0 / 1 rows at the interface.
+__global__ __launch_bounds__(1024) void eo_subset_kernel(
+    const float* __restrict__ LL, const float* __restrict__ log_prior, const int* __restrict__ labels, int N, int F,
+    int C, int min_size, int max_size, short* __restrict__ pop, float* __restrict__ pop_cost, int* __restrict__ born,
+    short* __restrict__ best, float* __restrict__ best_cost, float* __restrict__ hist,
+    unsigned long long* __restrict__ stats, EoArgs A, int TR, int w) {
+  extern __shared__ __attribute__((aligned(16))) float fs_tile[];
+  __shared__ float s_prior[FS_MAX_C];
+  __shared__ int s_cnt[3][SA_FS_MAX_CHAINS];
+  const int tid = threadIdx.x, nt = blockDim.x, FC = F * C, stride = FC | 1, P = A.P;
+  const unsigned magic = 0xFFFFFFFFu / (unsigned)FC + 1u;
+  const int ntiles = (N + TR - 1) / TR;
+  int* s_lab = reinterpret_cast<int*>(fs_tile + (size_t)TR * stride);  // [TR] labels of the staged rows
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wsh = __ffs(w) - 1, ci = wave >> wsh, sub = wave & (w - 1), cpw = (nt >> 6) >> wsh;
+  const long long p = (long long)blockIdx.x * cpw + ci;
+  const bool live = p < A.I;
+  if (tid < C) s_prior[tid] = log_prior[tid];
+  if (tid < 3 * SA_FS_MAX_CHAINS) (&s_cnt[0][0])[tid] = 0;
+  EoLanes pool{0u, 0.f, 0, lane, nullptr, false};
+  EoIsland S{0.f, 0, 0, 0};
+  unsigned bmk = 0, cand = 0;
+  if (live) {
+    pool.gborn = born + p * P;
+    pool.writer = sub == 0;
+    if (lane < P) {
+      const short* row = pop + (p * P + lane) * F;
+      for (int f = 0; f < F; ++f) pool.mk |= (unsigned)(row[f] != 0) << f;
+      pool.c = pop_cost[p * P + lane];
+      pool.a = eo_rank(pool.gborn, P, lane);
+    }
+    const bool in = lane < F;
+    bmk = (unsigned)__ballot(in && best[p * F + (in ? lane : 0)] != 0);
+    S.bc = best_cost[p];
+  }
+  __syncthreads();
+  bool staged = false;
+  int k = 0;  // iteration of this launch
+  int pos = 0;
+  eo_island(
+      A, (unsigned long long)(A.island_base + p), live, live && sub == 0 && lane == 0, S, pool,
+      hist + (live ? p : 0) * A.iters,
+      [&](int j) { cand = (unsigned)__builtin_amdgcn_readlane((int)pool.mk, __builtin_amdgcn_readfirstlane(j)); },
+      [&](unsigned qp, unsigned) {
+        pos = min((int)(av::u32_to_unit(qp) * (float)F), F - 1);
+        cand = (unsigned)__builtin_amdgcn_readfirstlane((int)(cand ^ (1u << pos)));
+      },
+      [&] {
+        const int sz = __popc(cand);
+        return sz >= min_size && sz <= max_size;
+      },
+      [&] { cand = (unsigned)__builtin_amdgcn_readfirstlane((int)(cand ^ (1u << pos))); },
+      [&](bool ok) {  // the scoring of sa_subset_kernel's price
+        int* cnt = s_cnt[k % 3];
+        if (tid < SA_FS_MAX_CHAINS) s_cnt[(k + 1) % 3][tid] = 0;
+        ++k;
+        int n = 0;
+        for (int t = 0; t < ntiles; ++t) {
+          const long long n0 = (long long)t * TR;
+          const int nr = min(TR, N - (int)n0);
+          if (ntiles > 1 || !staged) {
+            fs_stage(fs_tile, LL, n0, nr, FC, stride, magic, tid, nt);
+            for (int e = tid; e < nr; e += nt) s_lab[e] = labels[n0 + e];
+            staged = true;
+            __syncthreads();
+          }
+          if (ok) {
+            const int ng = (nr + 63) >> 6;
+            for (int gq = sub; gq < ng; gq += w) {
+              const int row = gq * 64 + lane;
+              const int rr = min(row, nr - 1);  // lanes past the tile score its last row, uncounted
+              const bool miss = fs_row_miss_uniform(fs_tile + rr * stride, s_prior, C, cand, s_lab[rr]);
+              n += __popcll(__ballot(miss && row < nr));
+            }
+            if (t == ntiles - 1 && lane == 0 && n) atomicAdd(&cnt[ci], n);
+          }
+          __syncthreads();  // the counts are in; the tile may be staged again
+        }
+        return (float)__builtin_amdgcn_readfirstlane(cnt[ci]) / (float)N;
+      },
+      [&](int j) {
+        if (lane == j) pool.mk = cand;
+      },
+      [&] { bmk = cand; });
+  if (live && sub == 0) {
+    if (lane < P) {
+      short* row = pop + (p * P + lane) * F;
+      for (int f = 0; f < F; ++f) row[f] = (short)((pool.mk >> f) & 1u);
+      pop_cost[p * P + lane] = pool.c;
+    }
+    if (lane < F) best[p * F + lane] = (short)((bmk >> lane) & 1u);
+    if (lane == 0) {
+      best_cost[p] = S.bc;
+      eo_report(stats, S);
+    }
+  }
+}
+
 }  // namespace
 
 namespace avk {
@@ -1453,6 +1913,91 @@ void tabu_assign(const float* cost, int L, int V, const uint8_t* conflict, short
     tabu_assign_kernel<false><<<grid, 64 * pl.waves, pl.lds, stream>>>(cost, L, V, conflict, sol, cur_cost, best_sol,
                                                                       best_cost, tabu, hist, P, (int)iters,
                                                                       (int)it_begin, (int)tenure, stats);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+// IW = the largest of 64, 32, ..., 1 islands per wave whose columns fit beside `shared` bytes;
+// IW = 0 (no kernel) when one island does not fit
+static EoPlan eo_plan(size_t per, size_t shared) {
+  for (int iw = 64; iw >= 1; iw >>= 1)
+    if (shared + iw * per <= EO_LDS_LIMIT) return EoPlan{iw, shared + iw * per};
+  return EoPlan{0, shared + per};
+}
+
+EoPlan eo_assign_plan(int P, int L) { return eo_plan(eo_island_bytes(P, L, 0), 0); }
+
+EoPlan eo_meeting_plan(int P, int M) {
+  return eo_plan(eo_island_bytes(P, 3 * (size_t)M, M), (size_t)MT_DOM_INTS * sizeof(int));
+}
+
+static EoArgs eo_args(const char* who, const EoRun& r, int I, int P) {
+  if (P < 2 || P > 64 || r.select < 1 || r.select > P)
+    throw std::invalid_argument(std::string(who) + ": 2 <= P <= 64, 1 <= select <= P");
+  if (r.iters < 0 || r.it_begin < 0 || r.iters >= (1LL << 31) || r.it_begin >= (1LL << 31) ||
+      r.it_begin + r.iters + P >= (1LL << 31))
+    throw std::invalid_argument(std::string(who) + ": 0 <= iters, it_begin and it_begin + iters + P < 2^31");
+  if (!(r.w >= 0.f && r.w <= 1.f) || !(r.age_scale >= 0.f && r.age_scale < INFINITY))
+    throw std::invalid_argument(std::string(who) + ": 0 <= w <= 1, 0 <= age_scale < inf");
+  return EoArgs{I, P, (int)r.iters, r.select, (int)r.it_begin, r.w, r.age_scale, r.seed, r.island_base};
+}
+
+// f(std::integral_constant<int, IW>) for the plan's IW
+template <class F>
+static void eo_with_iw(int iw, F f) {
+  switch (iw) {
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 1>{}); break;
+  }
+}
+
+void eo_assign(const float* cost, int L, int V, const uint8_t* conflict, int swap, short* pop, float* pop_cost,
+               int* born, short* best, float* best_cost, float* hist, unsigned long long* stats, int I, int P,
+               const EoRun& run, hipStream_t stream) {
+  if (L < 1 || V < 2 || V > 32767) throw std::invalid_argument("eo_assign: L >= 1, 2 <= V <= 32767");
+  const EoArgs A = eo_args("eo_assign", run, I, P);
+  const EoPlan pl = eo_assign_plan(P, L);
+  if (!pl.islands) throw std::invalid_argument("eo_assign: an island's pool exceeds 64 KiB of LDS");
+  if (I <= 0 || run.iters == 0) return;
+  eo_with_iw(pl.islands, [&](auto iw) {
+    constexpr int IW = decltype(iw)::value;
+    eo_assign_kernel<IW><<<(I + IW - 1) / IW, 64, pl.lds, stream>>>(cost, L, V, conflict, swap, pop, pop_cost, born,
+                                                                    best, best_cost, hist, stats, A);
+  });
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+void eo_meeting(const GaMeetingDomain& dom, short* pop, float* pop_cost, int* born, short* best, float* best_cost,
+                float* hist, unsigned long long* stats, int I, int P, const EoRun& run, hipStream_t stream) {
+  mt_check("eo_meeting", dom);
+  const EoArgs A = eo_args("eo_meeting", run, I, P);
+  const EoPlan pl = eo_meeting_plan(P, dom.M);
+  if (!pl.islands) throw std::invalid_argument("eo_meeting: an island's pool exceeds 64 KiB of LDS");
+  if (I <= 0 || run.iters == 0) return;
+  eo_with_iw(pl.islands, [&](auto iw) {
+    constexpr int IW = decltype(iw)::value;
+    eo_meeting_kernel<IW><<<(I + IW - 1) / IW, 64, pl.lds, stream>>>(dom, pop, pop_cost, born, best, best_cost, hist,
+                                                                     stats, A);
+  });
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+// the workgroup plan is sa_subset's: islands of `waves_per_island` waves (0: the launcher's choice)
+void eo_subset(const float* LL, const float* log_prior, const int* labels, int N, int F, int C, int min_size,
+               int max_size, short* pop, float* pop_cost, int* born, short* best, float* best_cost, float* hist,
+               unsigned long long* stats, int I, int P, const EoRun& run, int waves_per_island, hipStream_t stream) {
+  fs_check(N, F, C, "eo_subset");
+  const EoArgs A = eo_args("eo_subset", run, I, P);
+  const SaSubsetPlan pl = sa_subset_plan(N, F, C, std::max(I, 1), waves_per_island);
+  if (pl.lds > 56 * 1024) throw std::invalid_argument("eo_subset: the row tile exceeds its LDS");
+  if (I <= 0 || run.iters == 0) return;
+  eo_subset_kernel<<<pl.grid, pl.threads, pl.lds, stream>>>(LL, log_prior, labels, N, F, C, min_size, max_size, pop,
+                                                           pop_cost, born, best, best_cost, hist, stats, A, pl.rows,
+                                                           pl.waves);
   AV_HIP_CHECK(hipGetLastError());
 }
 

@@ -212,11 +212,9 @@ def _set(c: np.ndarray, pos: np.ndarray, v: np.ndarray) -> None:
     np.put_along_axis(c, pos[..., None], v[..., None], axis=-1)
 
 
-def ga_assign_reference(cost: np.ndarray, conflict: np.ndarray | None, invalid: float, pop: np.ndarray,
-                        pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool, mutate: bool,
-                        seed: int, island_base: int, gen_base: int = 0,
-                        swap: bool = True) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Host twin of ``ga_assign_kernel`` (all islands at once).  Returns (pop, pop_cost, hist)."""
+def ga_assign_domain(cost: np.ndarray, conflict: np.ndarray | None, invalid: float, swap: bool = True) -> GaDomain:
+    """What an assignment domain is to the island frames (``ga_assign_kernel``, ``eo_assign_kernel``):
+    cost [L, V], conflict [L, L] or None (its upper triangle counts, as in the kernels)."""
     cost = np.ascontiguousarray(cost, dtype=np.float32)
     conf = None
     if conflict is not None:
@@ -239,9 +237,17 @@ def ga_assign_reference(cost: np.ndarray, conflict: np.ndarray | None, invalid: 
         _set(cand, pos, v)
         return cand
 
-    dom = GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16), ncut=L, scale=1,
-                   crossover=splice, mutated=mutated, valid=lambda c: _valid(conf, c),
-                   price=lambda kids: ga_price(cost, conf, invalid, kids))
+    return GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16), ncut=L, scale=1,
+                    crossover=splice, mutated=mutated, valid=lambda c: _valid(conf, c),
+                    price=lambda kids: ga_price(cost, conf, invalid, kids))
+
+
+def ga_assign_reference(cost: np.ndarray, conflict: np.ndarray | None, invalid: float, pop: np.ndarray,
+                        pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool, mutate: bool,
+                        seed: int, island_base: int, gen_base: int = 0,
+                        swap: bool = True) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host twin of ``ga_assign_kernel`` (all islands at once).  Returns (pop, pop_cost, hist)."""
+    dom = ga_assign_domain(cost, conflict, invalid, swap)
     return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
 
 

@@ -177,16 +177,21 @@ def _mutated(tables: dict, c: np.ndarray, qp: np.ndarray, qv: np.ndarray) -> np.
     return cand
 
 
+def ga_meeting_domain(tables: dict) -> GaDomain:
+    """What a meeting-schedule domain is to the island frames (``ga_meeting_kernel``, ``eo_meeting_kernel``);
+    the cut falls between two meetings."""
+    return GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16),
+                    ncut=tables["M"], scale=3, crossover=splice, mutated=lambda c, qp, qv: _mutated(tables, c, qp, qv),
+                    valid=lambda c: ga_meeting_valid(tables, c), price=lambda kids: ga_meeting_price(tables, kids))
+
+
 def ga_meeting_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
                          purge_first: bool, mutate: bool, seed: int, island_base: int,
                          gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Host twin of ``ga_meeting_kernel`` (all islands at once).  Returns (pop int16, cost float32,
     hist float32)."""
-    # the cut falls between two meetings
-    dom = GaDomain(encode=lambda p: np.array(p, dtype=np.int64), decode=lambda p: p.astype(np.int16),
-                   ncut=tables["M"], scale=3, crossover=splice, mutated=lambda c, qp, qv: _mutated(tables, c, qp, qv),
-                   valid=lambda c: ga_meeting_valid(tables, c), price=lambda kids: ga_meeting_price(tables, kids))
-    return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
+    return ga_islands_reference(ga_meeting_domain(tables), pop, pop_cost, G, m, r, purge_first, mutate, seed,
+                                island_base, gen_base)
 
 
 _DEV_KEYS = ("days", "hours", "minutes", "dur", "share", "member", "role_w", "blocked", "ordered")
@@ -263,3 +268,23 @@ def sa_meeting_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: fl
         raise ValueError("the domain is outside the meeting kernel's limits")
     return sa_meeting_advance(tables, sol, cost, SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset,
                                                        it_begin, temp_start, chain_base), device, best, best_cost)
+
+
+# ---- evolutionary islands (optim.hip::eo_meeting_kernel, frame: optimize/eo.py) ------------------------
+def eo_meeting_advance(tables: dict, pop, cost, run, device, born=None, best=None, best_cost=None):
+    """One segment of :class:`~avenir_amd.optimize.eo.EoRun` ``run``: ``eo_meeting_kernel`` on a GPU, on the
+    host its twin — the island frame of :mod:`~avenir_amd.optimize.eo` with the island GA's mutation,
+    ``mt_valid`` and ``mt_cost``.  Returns (best int16, best_cost, stats, pop int16, cost, born, hist)."""
+    from .eo import _numpy_state, eo_islands_launch, eo_islands_reference
+    if torch.device(device).type == "cuda":
+        from .. import _native
+        return eo_islands_launch(_native.C().eo_meeting, tuple(_device_tables(tables, torch.device(device))), pop, cost,
+                                 run, born, best, best_cost, torch.device(device))
+    return eo_islands_reference(ga_meeting_domain(tables), *_numpy_state(pop, cost), run,
+                                *_numpy_state(born, best, best_cost))
+
+
+def eo_meeting_reference(tables: dict, pop, cost, run, born=None, best=None, best_cost=None, trace: dict | None = None):
+    """Host twin of ``eo_meeting_kernel`` (:func:`~avenir_amd.optimize.eo.eo_islands_reference`)."""
+    from .eo import eo_islands_reference
+    return eo_islands_reference(ga_meeting_domain(tables), pop, cost, run, born, best, best_cost, trace)

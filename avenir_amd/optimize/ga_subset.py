@@ -38,6 +38,12 @@ ROW_CAP = 1 << 15
 # one chain of 300 moves took 145 ms against 170 ms at 2^17 rows and 288 ms against 171 ms at 2^18
 # (profiles/sa_subset_cap_sweep.jsonl); 1,024 chains still win 5.6 x at 2^16 rows
 SA_ROW_CAP = 1 << 17
+# EvolutionaryOptimizer takes the island engine by default up to this many rows (search._island_engine):
+# one island is one workgroup that streams every row once per iteration, and one island of 300
+# iterations took 147 ms against 326 ms at 2^17 rows, 288 ms against 307 ms at 2^18 (inside the spread
+# of the runs: no win) and 578 ms against 288 ms at 2^19 (profiles/eo_subset_cap_sweep.jsonl); 1,024
+# islands still win 6.5 x at 2^16 rows
+EO_ROW_CAP = 1 << 17
 _F = np.float32
 
 
@@ -200,24 +206,30 @@ def ga_subset_init(tables: dict, n_islands: int, P: int, seed: int, island_base:
                           n_islands, P, seed, island_base, max_try)
 
 
-def ga_subset_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
-                        purge_first: bool, mutate: bool, seed: int, island_base: int,
-                        gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Host twin of ``ga_subset_kernel`` (all islands at once).  Returns (pop int16, cost float32,
-    hist float32)."""
+def ga_subset_domain(tables: dict, price=None) -> GaDomain:
+    """What a feature-subset domain is to the island frames (``ga_subset_kernel``, ``eo_subset_kernel``): a
+    solution is one uint32 mask, a mutation flips one bit (the value draw is unused)."""
     F = tables["F"]
 
     def crossover(A, B, cut):
         low = ((np.uint64(1) << cut.astype(np.uint64)) - np.uint64(1)).astype(np.uint32)      # cut <= 31
         return (A & low) | (B & ~low), (B & low) | (A & ~low)
 
-    def mutated(c, qp, qv):                      # the value draw is unused: a 0 / 1 position flips
+    def mutated(c, qp, qv):
         return c ^ (np.uint32(1) << _unit_index(u32_to_unit(qp), F).astype(np.uint32))
 
-    dom = GaDomain(encode=pack_masks, decode=lambda mk: unpack_masks(mk, F), ncut=F, scale=1, crossover=crossover,
-                   mutated=mutated, valid=lambda c: ga_subset_valid(tables, c),
-                   price=lambda kids: ga_subset_price(tables, kids))
-    return ga_islands_reference(dom, pop, pop_cost, G, m, r, purge_first, mutate, seed, island_base, gen_base)
+    return GaDomain(encode=pack_masks, decode=lambda mk: unpack_masks(mk, F), ncut=F, scale=1, crossover=crossover,
+                    mutated=mutated, valid=lambda c: ga_subset_valid(tables, c),
+                    price=price or (lambda kids: ga_subset_price(tables, kids)))
+
+
+def ga_subset_reference(tables: dict, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int,
+                        purge_first: bool, mutate: bool, seed: int, island_base: int,
+                        gen_base: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host twin of ``ga_subset_kernel`` (all islands at once).  Returns (pop int16, cost float32,
+    hist float32)."""
+    return ga_islands_reference(ga_subset_domain(tables), pop, pop_cost, G, m, r, purge_first, mutate, seed,
+                                island_base, gen_base)
 
 
 def ga_subset_run(domain, pop: np.ndarray, pop_cost: np.ndarray, G: int, m: int, r: int, purge_first: bool,
@@ -299,3 +311,41 @@ def sa_subset_run(domain, sol: np.ndarray, cost: np.ndarray, iters: int, t0: flo
         raise ValueError("sol must be [chains, F]")
     run = SaRun(iters, t0, cool, interval, geometric, max_retry, seed, offset, it_begin, temp_start, chain_base)
     return sa_subset_advance(tables, sol, cost, run, device, best, best_cost, waves_per_chain)
+
+
+# ---- evolutionary islands (optim.hip::eo_subset_kernel, frame: optimize/eo.py) -------------------------
+def eo_subset_advance(tables: dict, pop, cost, run, device, born=None, best=None, best_cost=None,
+                      waves_per_island: int = 0):
+    """One segment of :class:`~avenir_amd.optimize.eo.EoRun` ``run``: ``eo_subset_kernel`` on a GPU
+    (``waves_per_island`` = 0 lets the launcher choose; no result depends on it), on the host its twin —
+    the island frame of :mod:`~avenir_amd.optimize.eo` over 32-bit masks: a mutation flips one bit, a
+    mask is valid inside the size range and costs ``(float)errors / (float)N``; the twin scores a mask
+    once per call.  Returns (best int16 0 / 1 rows, best_cost, stats, pop int16, cost, born, hist)."""
+    from .eo import _numpy_state, eo_islands_launch, eo_islands_reference
+    if torch.device(device).type == "cuda":
+        from .. import _native
+        device = torch.device(device)
+        kernel = lambda *a: _native.C().eo_subset(*a, int(waves_per_island))
+        head = (*_device_tables(tables, device), tables["min_size"], tables["max_size"])
+        return eo_islands_launch(kernel, head, pop, cost, run, born, best, best_cost, device)
+    pop, cost, born, best, best_cost = _numpy_state(pop, cost, born, best, best_cost)
+    for s in (pop, best):
+        if s is not None and np.size(s) and (np.min(s) < 0 or np.max(s) > 1):
+            raise ValueError("eo_subset: masks must be 0 or 1")
+    N = _F(tables["N"])
+    seen: dict = {}
+
+    def price(mk):                                           # only valid masks are priced
+        flat = np.asarray(mk, dtype=np.uint32).reshape(-1)
+        new = np.array(sorted(set(flat.tolist()) - seen.keys()), dtype=np.uint32)
+        if new.size:
+            seen.update(zip(new.tolist(), subset_errors_reference(tables, new).tolist()))
+        return (np.array([seen[m] for m in flat.tolist()], dtype=np.float32) / N).reshape(np.shape(mk))
+
+    return eo_islands_reference(ga_subset_domain(tables, price), pop, cost, run, born, best, best_cost)
+
+
+def eo_subset_reference(tables: dict, pop, cost, run, born=None, best=None, best_cost=None, trace: dict | None = None):
+    """Host twin of ``eo_subset_kernel`` (:func:`~avenir_amd.optimize.eo.eo_islands_reference`)."""
+    from .eo import eo_islands_reference
+    return eo_islands_reference(ga_subset_domain(tables), pop, cost, run, born, best, best_cost, trace)

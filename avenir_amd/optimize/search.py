@@ -27,6 +27,13 @@ Tabu search over an :class:`AssignmentDomain` on a GPU is one launch of ``tabu_a
 L x V neighbourhood scored and reduced inside the wave every iteration), bit-equal to its numpy
 twin; the torch path (three [P, L, V] tensors, a validity GEMM and five host reads per iteration)
 stays the CPU default.
+The evolutionary optimiser over assignment, meeting-schedule and feature-subset domains on a GPU is
+one launch of ``eo_assign_kernel`` / ``eo_meeting_kernel`` (optimize/eo.py: one island per lane; pool,
+costs, age ranks and clone in lane-private LDS columns; tournament, mutation with take-back, pricing
+and purge inside the lane every iteration) or ``eo_subset_kernel`` (1 to 16 waves per island over a
+shared row tile, one pool member per lane in registers), bit-equal to its numpy twin, with global
+islands and explicit resumable state; its torch path (about 15 launches and a host read per
+iteration) stays the CPU default and serves callback and grouped domains.
 Other domains take batched tensor ops per generation; the GA over them runs one generation per
 ISLAND (each island draws from its own generator, keyed by global island index, so that results do
 not depend on the world size): ~12 small launches per island per generation.  Measured on one
@@ -582,16 +589,162 @@ class GeneticAlgorithm:
 class EvolutionaryOptimizer:
     """Mutation-only steady-state evolution (P/mlextra/optpopu.py:32-96), all islands at once:
     tournament-select the best of ``select`` random pool members, mutate a clone, purge the member
-    with the worst ``w * cost + (1 - w) * age`` and insert the child."""
+    with the worst ``w * cost + (1 - w) * age`` and insert the child.
+
+    On a GPU, assignment, meeting-schedule and feature-subset domains run as ONE launch per run or
+    checkpoint segment (optimize/eo.py: ``eo_assign_kernel`` / ``eo_meeting_kernel``, one island per
+    lane, the pool in lane-private LDS columns; ``eo_subset_kernel``, 1 to 16 waves per island over a
+    shared row tile, the pool in registers; :meth:`_island_engine`), bit-equal to a numpy twin that
+    runs on the CPU with ``use_kernel=True``.  That path indexes islands GLOBALLY and keeps explicit
+    state, so it does not depend on the world size and works with ``recovery``.  The torch path
+    below is the CPU default, ``use_kernel=False`` and every other domain: about 15 small launches
+    and a host read per iteration, one generator per rank."""
 
     def __init__(self, domain: SearchDomain, islands: int = 4, pool: int = 5, select: int = 3, iters: int = 100,
-                 purge_cost_weight: float = 0.7, purge_age_scale: float = 1.0, seed: int = 0, comm: Comm | None = None):
+                 purge_cost_weight: float = 0.7, purge_age_scale: float = 1.0, seed: int = 0, comm: Comm | None = None,
+                 use_kernel: bool | None = None, recovery: RecoveryConfig | None = None, segment: int | None = None):
         self.d = domain
         self.I, self.Pp, self.k, self.iters = islands, pool, select, iters
         self.w, self.age_scale, self.seed, self.comm = purge_cost_weight, purge_age_scale, seed, comm
+        self.use_kernel = use_kernel    # None: the island kernel (optimize/eo.py) whenever it applies
+        self.recovery = recovery        # checkpoint / resume of the kernel path (utils/resilience)
+        self.segment = segment          # iterations per checkpointed segment (default iters / 10)
+
+    @classmethod
+    def from_properties(cls, domain, conf, islands: int = 1, **kw):
+        """``opti.*`` keys of P/mlextra/optpopu.py:37-43 (a :class:`~avenir_amd.utils.config.Configuration`)."""
+        return cls(domain, islands=islands, pool=conf.get_int("opti.pool.size")[0],
+                   select=conf.get_int("opti.pool.select.size")[0], iters=conf.get_int("opti.num.iter")[0],
+                   purge_cost_weight=conf.get_float("opti.purge.cost.weight")[0],
+                   purge_age_scale=conf.get_float("opti.purge.age.scale")[0], **kw)
+
+    def _island_engine(self):
+        """The one-launch island kernel that applies to this run, or None (the torch path of
+        :meth:`run`): no tied groups and the pool inside the frame's limits (``eo.eo_pool_ok``).  An
+        AssignmentDomain (2 <= V <= 32767) takes ``eo_assign_kernel``, a MeetingScheduleDomain within
+        ``meeting_tables``' limits ``eo_meeting_kernel`` — both while one island's columns fit 64 KiB
+        of LDS (``eo.eo_assign_plan`` / ``eo.eo_meeting_plan``) — and a FeatureSubsetDomain with the
+        built-in naive-Bayes evaluator within ``subset_tables``' limits ``eo_subset_kernel``
+        (optimize/ga_subset.py): on a GPU by default, on the CPU (their host twin) only when
+        ``use_kernel`` is True, so CPU default results are unchanged.  Measured against the torch
+        path on one MI355X (profiles/eo_islands_bench.jsonl, benchmarks/bench_eo_islands.py: 300
+        iterations, pool 5, select 3, whole runs, medians of 5): the 24 x 10 assignment 15 x / 11 x /
+        6.4 x faster at 1 / 64 / 4,096 islands (30 against 464 ms, 99 ms against 1.10 s, 182 ms
+        against 1.17 s), meetings (10 meetings, 20 people) 60 x / 44 x / 4.1 x (7.4 against 441 ms,
+        14.1 against 615 ms, 205 against 833 ms), churn subsets 60 x / 56 x / 26 x at 4,000 rows and
+        1 / 64 / 1,024 islands (4.6 against 278 ms, 5.1 against 283 ms, 11.6 against 298 ms) and
+        6.3 x / 6.8 x / 6.5 x at 65,536 rows (44 against 277 ms, 46 against 310 ms, 109 against
+        716 ms).  One subset island is one workgroup that streams every row once per iteration, so
+        a single island stops winning at 2^18 rows (288 against 307 ms, inside the runs' spread; 578
+        against 288 ms at 2^19: profiles/eo_subset_cap_sweep.jsonl): past ``ga_subset.EO_ROW_CAP`` =
+        2^17 rows (147 against 326 ms) the default stays on the torch path and ``use_kernel=True``
+        still forces the engine.  No other measured configuration loses, so assignments and
+        meetings have no cap beyond the LDS limit.  Not measured: the kernels alone (the times
+        include the host-drawn start pools, their pricing and the copies), pools above 5,
+        multi-GPU runs."""
+        d = self.d
+        if self.use_kernel is False or getattr(d, "groups", None):
+            return None
+        if not (self.use_kernel is True or d.device.type == "cuda"):
+            return None
+        from . import eo, ga, ga_meeting as gm, ga_subset as gs
+        if not eo.eo_pool_ok(self.Pp, self.k, self.w, self.age_scale, self.iters):
+            return None
+        if isinstance(d, AssignmentDomain):
+            if not 2 <= d.V <= 32767 or eo.eo_assign_plan(self.Pp, d.L)[0] == 0:
+                return None
+            return _Islands(("eo_assign_kernel", "eo_assign_twin"), partial(ga.ga_assign_init, d),
+                            partial(eo.eo_assign_advance, d))
+        tb = gm.meeting_tables(d)           # None unless a MeetingScheduleDomain within the kernel's limits
+        if tb is not None and eo.eo_meeting_plan(self.Pp, tb["M"])[0] > 0:
+            def init(n, P, seed, island_base):
+                pop = gm.ga_meeting_init(tb, n, P, seed, island_base)
+                return pop, gm.ga_meeting_price(tb, pop)
+            return _Islands(("eo_meeting_kernel", "eo_meeting_twin"), init, partial(gm.eo_meeting_advance, tb))
+        if getattr(d, "loglik", None) is not None and d.loglik.dim() == 3:
+            tb = gs.subset_tables(d)        # None unless a FeatureSubsetDomain with the built-in evaluator
+            # one island is one workgroup streaming every row once per iteration: by default up to
+            # ga_subset.EO_ROW_CAP rows
+            if tb is not None and (self.use_kernel is True or tb["N"] <= gs.EO_ROW_CAP):
+                def init(n, P, seed, island_base):
+                    pop = gs.ga_subset_init(tb, n, P, seed, island_base)
+                    return pop, gs.ga_subset_price(tb, gs.pack_masks(pop), d.device)
+                return _Islands(("eo_subset_kernel", "eo_subset_host"), init, partial(gs.eo_subset_advance, tb))
+        return None
+
+    def _run_kernel(self, comm, engine) -> OptResult:
+        """K22 path.  Islands are GLOBAL: island ``g`` draws Philox streams keyed by ``g`` and starts
+        from the pool that ``ga_*_init`` draws for ``(seed, g)``; rank ``r`` runs islands ``[r I, (r + 1) I)``,
+        so the W-rank run equals one process with ``W I`` islands.  Under checkpointing the run is cut
+        into segments of ``segment`` iterations (one launch each, the same Philox counters and stamps
+        as one launch); rank 0 writes every island and a resume re-deals them by global index over
+        ANY world size.  ``history`` is the per-iteration minimum over all global islands, ``stats``
+        the counters ``inserted`` / ``stalls`` / ``improved`` summed over ranks, and ``engine``."""
+        from ..data.table import shard_range
+        from .eo import EoRun
+        d = self.d
+        W, r = comm.world, comm.rank
+        keys = ("pop", "cost", "born", "best", "best_cost", "hist")
+        names = ("inserted", "stalls", "improved")
+        stats = dict.fromkeys(names, 0)
+        b0 = 0
+        with IterationLoop("evolutionary", self.recovery, comm, device=d.device) as lp:
+            _, st, meta = lp.restore("cpu")
+            if st is not None:
+                total = int(meta["islands"])
+                a, e = shard_range(total, r, W)
+                pop, cost, born, best, bc, hist = (st[k][a:e].cpu().numpy() for k in keys)
+                b0 = int(meta["iters"])
+                if r == 0:                                       # global counters: summed over ranks at the end
+                    stats = dict(meta["stats"])
+            else:
+                total, a = self.I * W, r * self.I
+                pop, cost = engine.init(self.I, self.Pp, self.seed, a)
+                born = best = bc = None
+                hist = np.zeros((self.I, 0), dtype=np.float32)
+            seg = max(1, self.segment or -(-self.iters // 10)) if lp.enabled else max(1, self.iters)
+            for b in range(b0, self.iters, seg):
+                n = min(seg, self.iters - b)
+                with lp.step(b // seg):
+                    run = EoRun(n, self.k, self.w, self.age_scale, self.seed, b, a)
+                    best, bc, s, pop, cost, born, h = engine.run(pop, cost, run, d.device, born, best, bc)
+                hist = np.concatenate([hist, h], axis=1)
+                for k in names:
+                    stats[k] += s[k]
+                if lp.enabled:
+                    # int16 state travels as int32 (gloo has no int16)
+                    full = [comm.all_gather_v(torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32 if x.dtype == np.int16
+                                                                                    else x.dtype)))
+                            for x in (pop, cost, born, best, bc, hist)]
+                    lp.commit(b // seg, dict(zip(keys, full)),
+                              {"iters": b + n, "stats": self._global_stats(comm, stats, names), "islands": total},
+                              force=True)
+        if best is None:                                   # no iterations at all: the first smallest-cost member
+            ii, first = np.arange(pop.shape[0]), cost.argmin(1)
+            best, bc = pop[ii, first], cost[ii, first]
+        stats = self._global_stats(comm, stats, names)
+        stats["engine"] = engine.name(d.device)
+        ht = torch.from_numpy(np.ascontiguousarray(hist))
+        ha = comm.all_gather_v(ht) if comm.is_distributed else ht
+        history = ha.min(0).values.tolist() if ha.shape[0] else []
+        bs = torch.from_numpy(np.asarray(best).astype(np.int64)).to(d.device)
+        bct = torch.from_numpy(np.asarray(bc, dtype=np.float32)).to(d.device)
+        b, c = _global_best(comm, bct, bs)
+        return OptResult(b, c, bct, bs, history, stats)
+
+    @staticmethod
+    def _global_stats(comm, stats: dict, names) -> dict:
+        if not comm.is_distributed:
+            return dict(stats)
+        v = torch.tensor([stats[k] for k in names], dtype=torch.float64)
+        comm.all_reduce(v)
+        return dict(zip(names, (int(x) for x in v.tolist())))
 
     def run(self) -> OptResult:
         comm = self.comm or get_comm()
+        engine = self._island_engine()
+        if engine is not None:
+            return self._run_kernel(comm, engine)
         d, I, Pp, L = self.d, self.I, self.Pp, self.d.L
         dev = d.device
         gen = _gen(dev, self.seed + 104729 * comm.rank)
