@@ -1185,6 +1185,46 @@ py::tuple viterbi(const at::Tensor& obs, const at::Tensor& logA, const at::Tenso
   return py::make_tuple(path, score);
 }
 
+// Baum-Welch E-step (hmm.hip::hmm_estep_kernel): adds this call's expected counts (2^-32 fixed point,
+// int64) into trans [S, S], emit [S, O], init [S] and stats [4], writes Z / E of every row.
+void hmm_estep(const at::Tensor& obs, const at::Tensor& A, const at::Tensor& B, const at::Tensor& pi,
+               const at::Tensor& trans, const at::Tensor& emit, const at::Tensor& init, const at::Tensor& Z,
+               const at::Tensor& E, const at::Tensor& stats, const at::Tensor& workspace) {
+  CHECK_DEV(obs);
+  CHECK_DTYPE(obs, at::kShort);
+  TORCH_CHECK(obs.dim() == 2, "hmm_estep: obs must be [N, T]");
+  for (const at::Tensor* t : {&A, &B, &pi, &Z, &workspace}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kFloat);
+  }
+  for (const at::Tensor* t : {&trans, &emit, &init, &stats}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kLong);
+  }
+  CHECK_DEV(E);
+  CHECK_DTYPE(E, at::kInt);
+  for (const at::Tensor* t : {&A, &B, &pi, &trans, &emit, &init, &Z, &E, &stats, &workspace})
+    TORCH_CHECK(t->device() == obs.device(), "hmm_estep: every tensor must be on the device of obs");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "hmm_estep: A must be [S, S] and B [S, O]");
+  const int64_t S = A.size(0), O = B.size(1), N = obs.size(0), T = obs.size(1);
+  TORCH_CHECK(S >= 1 && S <= 64, "hmm_estep: 1 <= S <= 64 on the device");
+  TORCH_CHECK(A.size(1) == S, "hmm_estep: A must be [S, S]");
+  TORCH_CHECK(B.size(0) == S && O >= 1 && O <= 32767, "hmm_estep: B must be [S, 1 <= O <= 32767]");
+  TORCH_CHECK(pi.numel() == S, "hmm_estep: pi must be [S]");
+  TORCH_CHECK(trans.numel() == S * S && emit.numel() == S * O && init.numel() == S && stats.numel() == 4,
+              "hmm_estep: trans [S, S], emit [S, O], init [S], stats [4]");
+  TORCH_CHECK(Z.numel() == N && E.numel() == N, "hmm_estep: Z and E must be [N]");
+  TORCH_CHECK(N * T < (int64_t(1) << 31), "hmm_estep: N * T must stay below 2^31 observation steps");
+  TORCH_CHECK(workspace.numel() >= N * T * (S + 1), "hmm_estep: workspace needs N * T * (S + 1) floats");
+  DevGuard g(obs.device());
+  avk::hmm_estep(obs.data_ptr<int16_t>(), N, (int)T, (int)S, (int)O, A.data_ptr<float>(), B.data_ptr<float>(),
+                 pi.data_ptr<float>(), reinterpret_cast<unsigned long long*>(trans.data_ptr<int64_t>()),
+                 reinterpret_cast<unsigned long long*>(emit.data_ptr<int64_t>()),
+                 reinterpret_cast<unsigned long long*>(init.data_ptr<int64_t>()), Z.data_ptr<float>(),
+                 E.data_ptr<int>(), reinterpret_cast<unsigned long long*>(stats.data_ptr<int64_t>()),
+                 workspace.data_ptr<float>(), cur_stream(obs));
+}
+
 at::Tensor viterbi_chunks(const at::Tensor& obs, const at::Tensor& logA, const at::Tensor& logB,
                           const at::Tensor& logpi, int64_t n, int64_t obs_div, const c10::optional<at::Tensor>& bp) {
   CHECK_DEV(obs);
@@ -4683,6 +4723,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("cluster_accumulate", &cluster_accumulate);
   m.def("viterbi", &viterbi);
   m.def("viterbi_chunks", &viterbi_chunks);
+  m.def("hmm_estep", &hmm_estep);
   m.def("viterbi_backtrack", &viterbi_backtrack);
   m.def("markov_logodds", &markov_logodds);
   m.def("itemset_support", &itemset_support);

@@ -89,6 +89,15 @@ void viterbi_backtrack(const short* bp, const int* lens, const int* ends, long l
 void markov_logodds(const short* states, long long n, int L, const float* lr, int S, float* out,
                     hipStream_t stream);
 
+// ---- hmm.hip (K14b) -------------------------------------------------------------------------
+// Baum-Welch E-step over n sequences [n, T]: expected transition / emission / initial counts added
+// into trans [S, S], emit [S, O], init [S] as 2^-32 fixed point, stats (sequences, steps, empty,
+// impossible), per-sequence scaled normaliser Z [n] and binary exponent E [n]; workspace holds
+// n * T * (S + 1) floats.  1 <= S <= 64.
+void hmm_estep(const short* obs, long long n, int T, int S, int O, const float* A, const float* B,
+               const float* pi, unsigned long long* trans, unsigned long long* emit, unsigned long long* init,
+               float* Z, int* E, unsigned long long* stats, float* workspace, hipStream_t stream);
+
 // ---- assoc.hip (K17) -----------------------------------------------------------------------
 void itemset_support(const unsigned long long* P, int W, const unsigned long long* items,
                      const int* cand_prefix, const int* cand_item, int M, unsigned long long* support,

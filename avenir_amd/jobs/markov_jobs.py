@@ -66,6 +66,49 @@ def hmm_builder(args):
     return hmm
 
 
+@job("hiddenMarkovModelTrainer", "unsupervised / semi-supervised HMM training by Baum-Welch EM (beyond the reference; hmmt.*)")
+def hmm_trainer(args):
+    """Rows ``id..,obs,obs,...`` as ``viterbiStatePredictor`` reads them: the observations start
+    after ``hmmt.skip.field.count`` (default 1) fields and a token outside
+    ``hmmt.model.observations`` ends the sequence.  States are ``hmmt.model.states`` (names) or
+    ``hmmt.model.state.count`` (``s0..``).  ``hmmt.initial.model.path`` takes the lines
+    ``hiddenMarkovModelBuilder`` writes (fully or partially tagged estimate) as the start: the
+    semi-supervised use, and then the model's own states and observations hold; otherwise the start
+    is drawn from ``hmmt.seed``.  ``hmmt.max.iterations`` (50), ``hmmt.tolerance`` (1e-4),
+    ``hmmt.prior.count`` (0).  Each rank trains on its byte range of the input; the integer
+    expected-count tables are all-reduced once per iteration.  Output: the builder's layout
+    (integer rows scaled by ``hmmt.trans.prob.scale``, float rows when it is 1)."""
+    from ..data.table import _literal
+    from ..models.markov import HiddenMarkovModel, HiddenMarkovModelBuilder
+    ctx = JobContext(args, "hmmt.")
+    skip = ctx.get_int("skip.field.count", 1)
+    init = None
+    if ctx.get_str("initial.model.path", None):
+        init = HiddenMarkovModel.from_lines(ctx.all_lines(ctx.path("initial.model.path")), ",")
+        states, observations = init.states, init.observations
+    else:
+        observations = ctx.get_list("model.observations")
+        states = ctx.get_list("model.states", None) or [f"s{i}" for i in range(ctx.get_int("model.state.count"))]
+    lit = _literal(ctx.delim_in)
+    if lit is not None and len(lit) == 1:
+        rec = ctx.records(modes="x" * skip)
+        obs, _ = rec.padded(rec.map_codes(rec.codes, observations), start=skip, min_len=1)
+    else:   # regex delimiters: the split-row path
+        rows = ctx.rows()
+        oi = {o: i for i, o in enumerate(observations)}
+        L = max([len(r) - skip for r in rows] + [1])
+        obs = torch.tensor([[oi.get(t, -1) for t in r[skip:]] + [-1] * (L - len(r[skip:])) for r in rows],
+                           dtype=torch.int16).view(len(rows), L)
+    b = HiddenMarkovModelBuilder(states, observations, comm=ctx.comm)
+    fit = b.fit_unsupervised(obs.to(ctx.device), init=init, iters=ctx.get_int("max.iterations", 50),
+                             tol=ctx.get_float("tolerance", 1e-4), prior=ctx.get_float("prior.count", 0.0),
+                             seed=ctx.get_int("seed", 0))
+    ctx.emit_root(fit.model.to_lines(ctx.delim_out, ctx.get_int("trans.prob.scale", 1000)))
+    ctx.report({"job": "hiddenMarkovModelTrainer", "iterations": fit.iterations, "converged": fit.converged,
+                "logLikelihood": fit.log_likelihood[-1] if fit.log_likelihood else None, **fit.stats})
+    return fit
+
+
 # ================================================================================================
 # Markov chain classification
 # ================================================================================================

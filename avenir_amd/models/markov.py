@@ -162,6 +162,13 @@ class HiddenMarkovModel:
         lines.append(delim.join(fmt(x) for x in self.pi.cpu()))
         return lines
 
+    def posterior_counts(self, obs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Expected (transition [S, S], emission [S, O], initial [S]) counts of the observation
+        sequences ``obs`` [N, T] under this model (one Baum-Welch E-step, ``models/hmm_em.py``;
+        the HIP kernel for device tensors), float64 on the device of ``obs``."""
+        from .hmm_em import posterior_counts
+        return posterior_counts(self, obs)
+
     @classmethod
     def from_lines(cls, lines: list[str], delim: str = ",") -> "HiddenMarkovModel":
         lines = [ln for ln in lines if ln.strip()]
@@ -330,6 +337,33 @@ class HiddenMarkovModelBuilder:
         B = normalize_rows(emit, 1, self.laplace)
         pi = normalize_rows(init.view(1, -1), 1, self.laplace)[0]
         return HiddenMarkovModel(self.states, self.observations, A, B, pi)
+
+    def fit_unsupervised(self, obs: torch.Tensor, n_states: int | None = None, init: HiddenMarkovModel | None = None,
+                         iters: int = 50, tol: float | None = 1e-4, check_every: int = 1, prior: float = 0.0,
+                         seed: int = 0, workspace_bytes: int | None = None):
+        """Baum-Welch (EM) from observation sequences alone (``obs`` [N, T] int16, this rank's rows;
+        a negative or out-of-range value ends a row).  ``init`` is a model to refine — the output
+        of :meth:`fit` or of the partially tagged counts: the semi-supervised use; otherwise the
+        start is drawn on the host from ``seed`` alone (normalised ``1 + U(0, 1)`` rows), the same
+        on every device and at every world size.  ``n_states`` names the states ``s0..`` when the
+        builder has none.  Each iteration is one E-step (``hmm_estep_kernel`` on the device, its
+        numpy twin on the host: equal bit for bit), one all-reduce of the integer tables when
+        distributed, and the fp64 host M-step (``prior`` added to every count).  The log-likelihood
+        is tested every ``check_every`` iterations: the fit stops when the total rises by less than
+        ``tol * |total|``; ``tol=None`` runs ``iters`` iterations and never reads the per-sequence
+        normalisers back.  Returns :class:`avenir_amd.models.hmm_em.HmmFit`."""
+        from .hmm_em import fit_unsupervised
+        states = list(self.states or [])
+        if n_states is not None:
+            if not states:
+                states = [f"s{i}" for i in range(int(n_states))]
+            elif len(states) != int(n_states):
+                raise ValueError(f"n_states={n_states} but the builder has {len(states)} states")
+        if not states:
+            raise ValueError("fit_unsupervised needs the builder's states or n_states")
+        return fit_unsupervised(obs, states, list(self.observations), init=init, iters=iters, tol=tol,
+                                check_every=check_every, prior=prior, seed=seed, comm=self.comm,
+                                workspace_bytes=workspace_bytes)
 
 
 class ViterbiDecoder:
