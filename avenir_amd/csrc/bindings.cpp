@@ -267,6 +267,113 @@ void class_histogram_radix(const at::Tensor& dense, int64_t n, int64_t B, std::v
                              cur_stream(dense));
 }
 
+// Patched record streams: cells are 16-bit values below 2^15, held in int16 tensors.
+static int64_t patched_states(int64_t b, const std::vector<int64_t>& radices, int64_t class_radix) {
+  TORCH_CHECK(b >= 4 && b <= 14, "patched stream: 4..14 bits per record");
+  TORCH_CHECK(class_radix >= 1 && class_radix <= 3, "bad class radix");
+  int64_t J = class_radix;
+  for (int64_t r : radices) {
+    TORCH_CHECK(r >= 1 && r <= 9, "radix out of range");
+    J *= r;
+    TORCH_CHECK(J + 1 <= (int64_t(1) << 15), "patched stream: more than 2^15 cells");
+  }
+  TORCH_CHECK((int64_t(1) << b) < J, "patched stream: b must be below ceil(log2 J)");
+  return J;
+}
+
+// (stream, escaped records): the b-bit stream of cells and the count of records that store ESC
+std::tuple<at::Tensor, at::Tensor> pack_patched(const at::Tensor& words, int64_t n, int64_t b,
+                                                std::vector<int64_t> shifts, std::vector<int64_t> widths,
+                                                std::vector<int64_t> radices, std::vector<int64_t> bins_host,
+                                                int64_t label_shift, int64_t class_radix, int64_t n_classes,
+                                                const at::Tensor& state_cell) {
+  CHECK_DEV(words);
+  CHECK_DTYPE(words, at::kShort);
+  TORCH_CHECK(words.dim() == 1 && n >= 0 && n <= words.numel(), "words must be [>= n]");
+  const int64_t F = (int64_t)shifts.size();
+  TORCH_CHECK(F >= 1 && F <= 8, "1..8 packed fields");
+  const auto sh = radix_ints(shifts, F, "shifts"), wd = radix_ints(widths, F, "widths");
+  const auto rad = radix_ints(radices, F, "radices"), hb = radix_ints(bins_host, F, "bins");
+  const int64_t J = patched_states(b, radices, class_radix);
+  CHECK_DEV(state_cell);
+  CHECK_DTYPE(state_cell, at::kShort);
+  TORCH_CHECK(state_cell.is_contiguous() && state_cell.numel() == J && state_cell.device() == words.device(),
+              "state_cell must be [J] on the words' device");
+  auto dense = at::zeros({std::max<int64_t>(1, avk::dense_words(n, (int)b))}, words.options().dtype(at::kInt));
+  auto n_exc = at::zeros({1}, words.options().dtype(at::kLong));
+  DevGuard g(words.device());
+  avk::pack_patched(reinterpret_cast<const uint16_t*>(words.data_ptr()), n, (int)b, sh.data(), wd.data(), rad.data(),
+                    hb.data(), (int)F, (int)label_shift, (int)class_radix, (int)n_classes,
+                    reinterpret_cast<const uint16_t*>(state_cell.data_ptr()),
+                    reinterpret_cast<uint32_t*>(dense.data_ptr<int>()),
+                    reinterpret_cast<unsigned long long*>(n_exc.data_ptr<int64_t>()), cur_stream(words));
+  return {dense, n_exc};
+}
+
+// (exc_index int64 [n_exc], exc_cell int16 [n_exc]) of the escaped records, unsorted
+std::tuple<at::Tensor, at::Tensor> patch_exceptions(const at::Tensor& words, int64_t n, int64_t b,
+                                                    std::vector<int64_t> shifts, std::vector<int64_t> widths,
+                                                    std::vector<int64_t> radices, std::vector<int64_t> bins_host,
+                                                    int64_t label_shift, int64_t class_radix, int64_t n_classes,
+                                                    const at::Tensor& state_cell, int64_t n_exc) {
+  CHECK_DEV(words);
+  CHECK_DTYPE(words, at::kShort);
+  TORCH_CHECK(words.dim() == 1 && n >= 0 && n <= words.numel(), "words must be [>= n]");
+  TORCH_CHECK(n_exc >= 0 && n_exc <= n, "0 <= escaped records <= n");
+  const int64_t F = (int64_t)shifts.size();
+  TORCH_CHECK(F >= 1 && F <= 8, "1..8 packed fields");
+  const auto sh = radix_ints(shifts, F, "shifts"), wd = radix_ints(widths, F, "widths");
+  const auto rad = radix_ints(radices, F, "radices"), hb = radix_ints(bins_host, F, "bins");
+  const int64_t J = patched_states(b, radices, class_radix);
+  CHECK_DEV(state_cell);
+  CHECK_DTYPE(state_cell, at::kShort);
+  TORCH_CHECK(state_cell.is_contiguous() && state_cell.numel() == J && state_cell.device() == words.device(),
+              "state_cell must be [J] on the words' device");
+  auto idx = at::zeros({n_exc}, words.options().dtype(at::kLong));
+  auto cell = at::zeros({n_exc}, words.options().dtype(at::kShort));
+  auto fill = at::zeros({1}, words.options().dtype(at::kLong));
+  DevGuard g(words.device());
+  avk::patch_exceptions(reinterpret_cast<const uint16_t*>(words.data_ptr()), n, (int)b, sh.data(), wd.data(),
+                        rad.data(), hb.data(), (int)F, (int)label_shift, (int)class_radix, (int)n_classes,
+                        reinterpret_cast<const uint16_t*>(state_cell.data_ptr()), n_exc,
+                        reinterpret_cast<long long*>(idx.data_ptr<int64_t>()),
+                        reinterpret_cast<uint16_t*>(cell.data_ptr()),
+                        reinterpret_cast<unsigned long long*>(fill.data_ptr<int64_t>()), cur_stream(words));
+  return {idx, cell};
+}
+
+void class_histogram_patched(const at::Tensor& dense, int64_t n, int64_t b, std::vector<int64_t> radices,
+                             std::vector<int64_t> bins_host, std::vector<int64_t> offs_host, int64_t class_radix,
+                             int64_t total_bins, int64_t n_classes, at::Tensor& out, bool count_labels,
+                             const at::Tensor& exc_cell, const at::Tensor& cell_state) {
+  CHECK_DEV(dense);
+  CHECK_DTYPE(dense, at::kInt);
+  const int64_t J = patched_states(b, radices, class_radix);
+  TORCH_CHECK(n >= 0 && dense.is_contiguous() && dense.numel() >= avk::dense_words(n, (int)b),
+              "patched stream too short");
+  const int64_t F = (int64_t)radices.size();
+  TORCH_CHECK(F >= 1 && F <= 8, "1..8 packed fields");
+  const auto rad = radix_ints(radices, F, "radices"), hb = radix_ints(bins_host, F, "bins");
+  const auto ho = radix_ints(offs_host, F, "offs");
+  TORCH_CHECK(n_classes >= 1 && n_classes <= 2, "1 or 2 classes");
+  TORCH_CHECK(total_bins >= 1 && total_bins < (int64_t(1) << 24), "bad table width");
+  CHECK_DEV(exc_cell); CHECK_DTYPE(exc_cell, at::kShort);
+  CHECK_DEV(cell_state); CHECK_DTYPE(cell_state, at::kShort);
+  TORCH_CHECK(exc_cell.dim() == 1 && exc_cell.is_contiguous() && exc_cell.numel() <= n &&
+                  exc_cell.device() == dense.device(), "exc_cell must be [E <= n] on the stream's device");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(exc_cell.data_ptr()) % 16 == 0, "exc_cell must be 16-byte aligned");
+  TORCH_CHECK(cell_state.is_contiguous() && cell_state.numel() == J + 1 && cell_state.device() == dense.device(),
+              "cell_state must be [J + 1] on the stream's device");
+  CHECK_DEV(out); CHECK_DTYPE(out, at::kLong);
+  TORCH_CHECK(out.numel() == n_classes * total_bins && out.device() == dense.device(), "out must be [C * TB]");
+  DevGuard g(dense.device());
+  avk::class_histogram_patched(reinterpret_cast<const uint32_t*>(dense.data_ptr<int>()), n, (int)b, rad.data(),
+                               hb.data(), ho.data(), (int)F, (int)class_radix, (int)total_bins, (int)n_classes,
+                               count_labels ? 1 : 0, reinterpret_cast<const uint16_t*>(exc_cell.data_ptr()),
+                               exc_cell.numel(), reinterpret_cast<const uint16_t*>(cell_state.data_ptr()),
+                               reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()), cur_stream(dense));
+}
+
 int64_t radix_recip(int64_t d) {
   TORCH_CHECK(d >= 1 && d <= (int64_t(1) << 15), "divisor out of range");
   return (int64_t)avk::radix_recip((unsigned)d);
@@ -4685,6 +4792,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("radix_shape", &radix_shape);
   m.def("pack_radix", &pack_radix);
   m.def("class_histogram_radix", &class_histogram_radix);
+  m.def("pack_patched", &pack_patched);
+  m.def("patch_exceptions", &patch_exceptions);
+  m.def("class_histogram_patched", &class_histogram_patched);
   m.def("radix_recip", &radix_recip);
   m.def("bigram_histogram", &bigram_histogram);
   m.def("class_moments", &class_moments);

@@ -442,6 +442,22 @@ void pack_radix(const uint16_t* words, long long n, int B, const int* h_shift, c
 void class_histogram_radix(const uint32_t* dense, long long n, int B, const int* h_radix, const int* h_bins,
                            const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
                            int count_labels, unsigned long long* out, hipStream_t stream);
+// patched record streams (histogram.hip): 4 <= b < ceil(log2 J) bits per record; a record stores the cell
+// of its state (state_cell[J]; cell = frequency rank r below ESC = 2^b - 1, r + 1 from ESC on) or ESC,
+// and every escaped record is listed as (index, cell); cell_state[J + 1] is the inverse table (>= J: none).
+// pack_patched adds the number of escaped records to *n_exc; patch_exceptions fills both lists
+// (n_exc entries, in any order) through the zeroed counter *fill.
+void pack_patched(const uint16_t* words, long long n, int b, const int* h_shift, const int* h_width,
+                  const int* h_radix, const int* h_bins, int nfeat, int label_shift, int class_radix, int n_classes,
+                  const uint16_t* state_cell, uint32_t* dense, unsigned long long* n_exc, hipStream_t stream);
+void patch_exceptions(const uint16_t* words, long long n, int b, const int* h_shift, const int* h_width,
+                      const int* h_radix, const int* h_bins, int nfeat, int label_shift, int class_radix,
+                      int n_classes, const uint16_t* state_cell, long long n_exc, long long* exc_index,
+                      uint16_t* exc_cell, unsigned long long* fill, hipStream_t stream);
+void class_histogram_patched(const uint32_t* dense, long long n, int b, const int* h_radix, const int* h_bins,
+                             const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
+                             int count_labels, const uint16_t* exc_cell, long long n_exc, const uint16_t* cell_state,
+                             unsigned long long* out, hipStream_t stream);
 // multiply-high reciprocal floor(2^32 / d) + 1 the radix kernel divides cell indices with (0 for d < 2)
 unsigned radix_recip(unsigned d);
 // K1 device CSV parse (csv.hip)

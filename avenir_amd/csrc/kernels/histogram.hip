@@ -11,7 +11,8 @@
 //
 // Row-packed records (all codes + class of a record in <= 15 bits): hist_joint_radix_kernel counts
 // each record with ONE LDS atomic into the block's joint table (dense stream of mixed-radix codes,
-// 11 bits = 1.375 B/record for churn, the code being the table cell) and takes the class-conditional
+// 11 bits = 1.375 B/record for churn, the code being the table cell; or the patched stream of frequency
+// ranks, 10 bits for churn, with an exception list) and takes the class-conditional
 // marginals once per block — the NB training headline; hist_joint_dense_kernel streams the same
 // records as bit fields (13 bits for churn), hist_joint_kernel / hist_rowpack_kernel the 16-bit words.
 //
@@ -794,8 +795,25 @@ __device__ __forceinline__ unsigned div_small(unsigned n, unsigned d, unsigned m
   return d == 1u ? n : __umulhi(n, m);
 }
 
+// mixed-radix code of a 16-bit word of pack_rows; every digit is clamped to its radix, so a code is
+// < J whatever the word holds
+__device__ __forceinline__ uint32_t radix_code(uint32_t w, const RowPackSpec& spec, const RadixSpec& rs, int nfeat) {
+  uint32_t v = 0, mult = 1;
+  if (rs.crad > 1) {
+    const uint32_t lb = __builtin_amdgcn_ubfe(w, (unsigned)spec.lsh, 2u);
+    const uint32_t cd = lb == 1u ? 0u : (lb == 2u ? 1u : 2u);
+    v = min(cd, (uint32_t)rs.crad - 1u);
+    mult = (uint32_t)rs.crad;
+  }
+  for (int f = 0; f < nfeat; ++f) {
+    const uint32_t code = __builtin_amdgcn_ubfe(w, (unsigned)spec.sh[f], (unsigned)spec.w[f]);
+    v += min(code, (uint32_t)rs.rad[f] - 1u) * mult;
+    mult *= (uint32_t)rs.rad[f];
+  }
+  return v;
+}
+
 // 16-bit words of pack_rows -> dense B-bit stream of mixed-radix codes (container as pack_dense).
-// Every digit is clamped to its radix, so a code is < J whatever the words hold.
 __global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restrict__ words, long long n, int B,
                                                         RowPackSpec spec, RadixSpec rs, int nfeat,
                                                         uint32_t* __restrict__ dense) {
@@ -807,22 +825,7 @@ __global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restri
     for (int i = 0; i < 16; ++i) d[i] = 0;
     for (int k = 0; k < 32; ++k) {
       const long long r = (g << 5) + k;
-      uint32_t v = 0;
-      if (r < n) {
-        const uint32_t w = words[r];
-        uint32_t mult = 1;
-        if (rs.crad > 1) {
-          const uint32_t lb = __builtin_amdgcn_ubfe(w, (unsigned)spec.lsh, 2u);
-          const uint32_t cd = lb == 1u ? 0u : (lb == 2u ? 1u : 2u);
-          v = min(cd, (uint32_t)rs.crad - 1u);
-          mult = (uint32_t)rs.crad;
-        }
-        for (int f = 0; f < nfeat; ++f) {
-          const uint32_t code = __builtin_amdgcn_ubfe(w, (unsigned)spec.sh[f], (unsigned)spec.w[f]);
-          v += min(code, (uint32_t)rs.rad[f] - 1u) * mult;
-          mult *= (uint32_t)rs.rad[f];
-        }
-      }
+      const uint32_t v = r < n ? radix_code(words[r], spec, rs, nfeat) : 0u;
       const int bit = k * B, i = bit >> 5, sh = bit & 31;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {  // register-indexed writes unrolled (no scratch)
@@ -834,6 +837,93 @@ __global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Patched record stream: B = ceil(log2 J) bits pay for every joint state, the data for far fewer
+// (churn: 864 of 1080 states hold all but 6e-8 of the mass).  A record whose state is among the
+// 2^b - 1 most frequent stores that state's frequency rank in b < B bits; any other record stores the
+// escape code ESC = 2^b - 1 and is listed as (record index, cell) in a short exception list.  The
+// cell of rank r is r below ESC and r + 1 from ESC on, so the J + 1 cells (cell ESC a dummy) index
+// one joint table and the hot loop is the plain stream's at B = b.
+// ---------------------------------------------------------------------------------------------
+// cell of a word through the J-entry state -> cell table (in LDS)
+__device__ __forceinline__ uint32_t patched_cell(uint32_t w, const RowPackSpec& spec, const RadixSpec& rs, int nfeat,
+                                                 const uint16_t* s_cell) {
+  return s_cell[radix_code(w, spec, rs, nfeat)];
+}
+
+// 16-bit words -> dense b-bit stream of cells (container as pack_dense; ESC for a cell above ESC);
+// *n_exc counts the escaped records
+__global__ __launch_bounds__(HB) void pack_patched_kernel(const uint16_t* __restrict__ words, long long n, int b,
+                                                          RowPackSpec spec, RadixSpec rs, int J, int nfeat,
+                                                          const uint16_t* __restrict__ state_cell,
+                                                          uint32_t* __restrict__ dense,
+                                                          unsigned long long* __restrict__ n_exc) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t s_cell[];
+  for (int i = threadIdx.x; i < J; i += HB) s_cell[i] = state_cell[i];
+  __syncthreads();
+  const uint32_t esc = (1u << b) - 1u;
+  const long long groups = (n + 31) >> 5;
+  const long long stride = (long long)gridDim.x * HB;
+  unsigned long long mine = 0;
+  for (long long g = (long long)blockIdx.x * HB + threadIdx.x; g < groups; g += stride) {
+    uint32_t d[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) d[i] = 0;
+    for (int k = 0; k < 32; ++k) {
+      const long long r = (g << 5) + k;
+      uint32_t v = 0;
+      if (r < n) {
+        v = patched_cell(words[r], spec, rs, nfeat, s_cell);
+        if (v > esc) {
+          v = esc;
+          ++mine;
+        }
+      }
+      const int bit = k * b, i = bit >> 5, sh = bit & 31;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {  // register-indexed writes unrolled (no scratch)
+        if (q == i) d[q] |= v << sh;
+        if (q == i + 1 && sh + b > 32) d[q] |= v >> (32 - sh);
+      }
+    }
+    for (int i = 0; i < b; ++i) dense[g * b + i] = d[i];
+  }
+  if (mine) atomicAdd(n_exc, mine);
+}
+
+// the escaped records of pack_patched_kernel as (record index, cell), in any order; `cap` is the
+// count that kernel returned, the length of both arrays
+__global__ __launch_bounds__(HB) void patch_exceptions_kernel(const uint16_t* __restrict__ words, long long n, int b,
+                                                              RowPackSpec spec, RadixSpec rs, int J, int nfeat,
+                                                              const uint16_t* __restrict__ state_cell,
+                                                              long long* __restrict__ exc_index,
+                                                              uint16_t* __restrict__ exc_cell,
+                                                              unsigned long long* __restrict__ fill,
+                                                              unsigned long long cap) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t s_cell[];
+  for (int i = threadIdx.x; i < J; i += HB) s_cell[i] = state_cell[i];
+  __syncthreads();
+  const uint32_t esc = (1u << b) - 1u;
+  const long long stride = (long long)gridDim.x * HB;
+  for (long long r = (long long)blockIdx.x * HB + threadIdx.x; r < n; r += stride) {
+    const uint32_t v = patched_cell(words[r], spec, rs, nfeat, s_cell);
+    if (v > esc) {
+      const unsigned long long at = atomicAdd(fill, 1ull);
+      if (at < cap) {
+        exc_index[at] = r;
+        exc_cell[at] = (uint16_t)v;
+      }
+    }
+  }
+}
+
+// what hist_joint_radix_kernel<B, true> counts beside the stream (unused by <B, false>)
+struct PatchSpec {
+  const uint16_t* exc_cell;    // [n_exc] cells of the escaped records, 16-byte aligned
+  const uint16_t* cell_state;  // [J + 1] state of a cell; >= J: none
+  long long n_exc;
+};
+
 // One LDS atomic per record into s_joint[(code << log2 R) + lane % R]; the hot loop is
 // hist_joint_dense_kernel's (B dword loads per lane, 32 extractions at compile-time offsets) with a
 // single shift-add as the cell address.  Epilogue: S = min(R, 8) lanes share a cell's R replicas
@@ -843,17 +933,23 @@ __global__ __launch_bounds__(HB) void pack_radix_kernel(const uint16_t* __restri
 // cell's digits in turn (lane `part`: digits part, part + S, ...; the class-count column counts as
 // digit F) and add the count into the [C][TB] table, and that table is flushed with one global
 // atomic per non-zero entry.
-template <int B>
+//
+// P (patched stream, B = b): the stream holds cells, not states.  The table has J + 1 cells; after the
+// main loop the blocks add the exception list's cells (grid stride, clamped to J) into the same
+// replicas, and the epilogue maps a cell through cell_state before the digit decode (cell ESC, the
+// dummy every escaped record of the stream lands in, maps to no state and is skipped).
+template <int B, bool P>
 __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* __restrict__ dense, long long n,
                                                                 RadixSpec rs, int J, int log2r, int nfeat,
                                                                 int n_classes, int total_bins, int count_labels,
-                                                                unsigned long long* __restrict__ out) {
+                                                                unsigned long long* __restrict__ out, PatchSpec ps) {
   extern __shared__ __attribute__((aligned(16))) unsigned int s_joint[];
   constexpr unsigned M = (1u << B) - 1u;
   const int NT = (int)blockDim.x;
   const int R = 1 << log2r;
   const int ctb = n_classes * total_bins;
-  unsigned int* s_small = s_joint + ((size_t)J << log2r);
+  const int cells = P ? J + 1 : J;
+  unsigned int* s_small = s_joint + ((size_t)cells << log2r);
   const long long groups = (n + 31) >> 5;
   const long long stride = (long long)gridDim.x * NT;
   uint32_t d[B + 1];
@@ -865,7 +961,7 @@ __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* 
   };
   long long g = (long long)blockIdx.x * NT + threadIdx.x;
   if (g < groups) load(g);  // the first group is in flight while the tables are cleared
-  for (int i = threadIdx.x; i < (J << log2r) + ctb; i += NT) s_joint[i] = 0;
+  for (int i = threadIdx.x; i < (cells << log2r) + ctb; i += NT) s_joint[i] = 0;
   // byte address of a record's counter = lane base + (code << (log2 R + 2)): one v_lshl_add_u32
   char* const my = reinterpret_cast<char*>(s_joint + (threadIdx.x & (unsigned)(R - 1)));
   const unsigned lr = (unsigned)log2r + 2u;
@@ -888,17 +984,42 @@ __global__ __launch_bounds__(1024) void hist_joint_radix_kernel(const uint32_t* 
     g += stride;
     if (g < groups) load(g);
   }
+  if (P) {
+    // eight cells (one 16-byte load) per lane and round: a round is one load latency, and a long list
+    // walked a cell at a time would cost many of them; the last n_exc % 8 cells one by one
+    auto add = [&](unsigned c) __attribute__((always_inline)) {
+      atomicAdd(reinterpret_cast<unsigned int*>(my + (min(c, (unsigned)J) << lr)), 1u);
+    };
+    const long long octs = ps.n_exc >> 3;
+    const uint4* src = reinterpret_cast<const uint4*>(ps.exc_cell);
+    const long long first = (long long)blockIdx.x * NT + threadIdx.x;
+    for (long long e = first; e < octs; e += stride) {
+      const uint4 v = src[e];
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        add(w[k] & 0xFFFFu);
+        add(w[k] >> 16);
+      }
+    }
+    for (long long e = (octs << 3) + first; e < ps.n_exc; e += stride) add(ps.exc_cell[e]);
+  }
   __syncthreads();
   const int ls = log2r < 3 ? log2r : 3;  // S = 2^ls lanes per cell
   const int S = 1 << ls;
-  const int items = J << ls;
+  const int items = cells << ls;
   for (int base = 0; base < items; base += NT) {  // block-uniform bound: every lane takes part in the shuffles
     const int i = base + (int)threadIdx.x;
-    const unsigned cell = (unsigned)(i >> ls);
+    const unsigned slot = (unsigned)(i >> ls);
     unsigned cnt = 0;
     if (i < items)
-      for (int q = 0; q < (R >> ls); ++q) cnt += s_joint[((size_t)cell << log2r) + ((i + (q << ls)) & (R - 1))];
+      for (int q = 0; q < (R >> ls); ++q) cnt += s_joint[((size_t)slot << log2r) + ((i + (q << ls)) & (R - 1))];
     for (int o = S >> 1; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+    unsigned cell = slot;  // the state the digits are decoded from
+    if (P) {
+      cell = i < items && slot != M ? (unsigned)ps.cell_state[slot] : (unsigned)J;
+      if (cell >= (unsigned)J) cnt = 0;
+    }
     const unsigned c = cell - div_small(cell, (unsigned)rs.crad, rs.crcp) * (unsigned)rs.crad;  // crad = 1: class 0
     // an unknown class is not counted (as in the column histogram)
     if (i < items && cnt && c < (unsigned)n_classes) {
@@ -1445,19 +1566,20 @@ int radix_replicas(long long J, int n_classes, int total_bins) {
   return R;
 }
 
-template <int B>
+template <int B, bool P>
 static void launch_joint_radix(const uint32_t* dense, long long n, const RadixSpec& rs, int J, int nfeat,
                                int n_classes, int total_bins, int count_labels, unsigned long long* out,
-                               hipStream_t stream) {
-  const int R = radix_replicas(J, n_classes, total_bins);
-  const long long lds = 4LL * ((long long)J * R + (long long)n_classes * total_bins);
+                               const PatchSpec& ps, hipStream_t stream) {
+  const int cells = P ? J + 1 : J;  // patched: cell ESC is a dummy next to the J states
+  const int R = radix_replicas(cells, n_classes, total_bins);
+  const long long lds = 4LL * ((long long)cells * R + (long long)n_classes * total_bins);
   if (lds > kLdsPerCu) throw std::runtime_error("radix histogram: joint table exceeds LDS");
   int log2r = 0;
   while ((1 << log2r) < R) ++log2r;
   // threads per block: at least 16 waves per CU next to the tables that fit it
   const int per_cu = (int)(kLdsPerCu / lds);
   const int NT = per_cu >= 4 ? HB : (per_cu >= 2 ? 512 : 1024);
-  auto kern = hist_joint_radix_kernel<B>;
+  auto kern = hist_joint_radix_kernel<B, P>;
   // occupancy query and LDS opt-in once per (device, configuration), not per training step
   static int c_dev = -1, c_lds = -1, c_nt = 0, c_res = 0;
   int dev = 0;
@@ -1472,7 +1594,8 @@ static void launch_joint_radix(const uint32_t* dense, long long n, const RadixSp
     c_nt = NT;
   }
   const int grid = std::max(1, std::min(av::stream_grid(std::max(1LL, (n + 31) >> 5), NT, 1, 8192), c_res));
-  kern<<<grid, NT, (size_t)lds, stream>>>(dense, n, rs, J, log2r, nfeat, n_classes, total_bins, count_labels, out);
+  kern<<<grid, NT, (size_t)lds, stream>>>(dense, n, rs, J, log2r, nfeat, n_classes, total_bins, count_labels, out,
+                                          ps);
   AV_HIP_CHECK(hipGetLastError());
 }
 
@@ -1486,11 +1609,89 @@ void class_histogram_radix(const uint32_t* dense, long long n, int B, const int*
   if (count_labels && total_bins < 1) throw std::runtime_error("radix histogram: no class-count column");
   switch (B) {
 #define AV_RADIX(BB) \
-  case BB: launch_joint_radix<BB>(dense, n, rs, (int)J, nfeat, n_classes, total_bins, count_labels, out, stream); break;
+  case BB:                                                                                                  \
+    launch_joint_radix<BB, false>(dense, n, rs, (int)J, nfeat, n_classes, total_bins, count_labels, out, PatchSpec{}, \
+                                  stream);                                                                  \
+    break;
     AV_RADIX(4) AV_RADIX(5) AV_RADIX(6) AV_RADIX(7) AV_RADIX(8) AV_RADIX(9) AV_RADIX(10) AV_RADIX(11)
     AV_RADIX(12) AV_RADIX(13) AV_RADIX(14) AV_RADIX(15)
 #undef AV_RADIX
     default: throw std::runtime_error("radix histogram: 4..15 bits per record");
+  }
+}
+
+// ---- patched record streams ----
+// b bits per record next to the B = ceil(log2 J) of the plain stream: 4 <= b < B, and the J + 1 cells
+// fit the 16-bit cell and the exact range of div_small
+static void patched_check(long long J, int b) {
+  if (b < 4 || b > 14 || b >= radix_bits(J)) throw std::runtime_error("patched stream: 4 <= b < ceil(log2 J), b <= 14");
+  if (J + 1 > (1LL << 15)) throw std::runtime_error("patched stream: more than 2^15 cells");
+}
+
+static RowPackSpec patched_fields(const int* h_shift, const int* h_width, int nfeat, int label_shift, int n_classes) {
+  RowPackSpec spec{};
+  for (int k = 0; k < nfeat; ++k) {
+    if (h_width[k] < 1 || h_width[k] > 3 || h_shift[k] < 0 || h_shift[k] + h_width[k] > 16)
+      throw std::runtime_error("patched stream: fields of 1..3 bits inside the 16-bit word");
+    spec.sh[k] = h_shift[k];
+    spec.w[k] = h_width[k];
+  }
+  if (n_classes > 1 && (label_shift < 0 || label_shift + 2 > 16))
+    throw std::runtime_error("patched stream: the class is two one-hot bits inside the 16-bit word");
+  spec.lsh = n_classes > 1 ? label_shift : 0;
+  return spec;
+}
+
+void pack_patched(const uint16_t* words, long long n, int b, const int* h_shift, const int* h_width,
+                  const int* h_radix, const int* h_bins, int nfeat, int label_shift, int class_radix, int n_classes,
+                  const uint16_t* state_cell, uint32_t* dense, unsigned long long* n_exc, hipStream_t stream) {
+  if (n <= 0) return;
+  const int offs0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long J = 0;
+  const RadixSpec rs = radix_spec(h_radix, h_bins, offs0, nfeat, class_radix, n_classes, 1 << 30, &J);
+  patched_check(J, b);
+  const RowPackSpec spec = patched_fields(h_shift, h_width, nfeat, label_shift, n_classes);
+  pack_patched_kernel<<<av::stream_grid((n + 31) >> 5, HB, 1, 4096), HB, (size_t)J * sizeof(uint16_t), stream>>>(
+      words, n, b, spec, rs, (int)J, nfeat, state_cell, dense, n_exc);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+void patch_exceptions(const uint16_t* words, long long n, int b, const int* h_shift, const int* h_width,
+                      const int* h_radix, const int* h_bins, int nfeat, int label_shift, int class_radix,
+                      int n_classes, const uint16_t* state_cell, long long n_exc, long long* exc_index,
+                      uint16_t* exc_cell, unsigned long long* fill, hipStream_t stream) {
+  if (n <= 0 || n_exc <= 0) return;
+  const int offs0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long J = 0;
+  const RadixSpec rs = radix_spec(h_radix, h_bins, offs0, nfeat, class_radix, n_classes, 1 << 30, &J);
+  patched_check(J, b);
+  const RowPackSpec spec = patched_fields(h_shift, h_width, nfeat, label_shift, n_classes);
+  patch_exceptions_kernel<<<av::stream_grid(n, HB, 1, 4096), HB, (size_t)J * sizeof(uint16_t), stream>>>(
+      words, n, b, spec, rs, (int)J, nfeat, state_cell, exc_index, exc_cell, fill, (unsigned long long)n_exc);
+  AV_HIP_CHECK(hipGetLastError());
+}
+
+void class_histogram_patched(const uint32_t* dense, long long n, int b, const int* h_radix, const int* h_bins,
+                             const int* h_offs, int nfeat, int class_radix, int total_bins, int n_classes,
+                             int count_labels, const uint16_t* exc_cell, long long n_exc, const uint16_t* cell_state,
+                             unsigned long long* out, hipStream_t stream) {
+  if (n <= 0) return;
+  long long J = 0;
+  const RadixSpec rs = radix_spec(h_radix, h_bins, h_offs, nfeat, class_radix, n_classes, total_bins, &J);
+  patched_check(J, b);
+  if (n_exc < 0 || (n_exc > 0 && !exc_cell) || (reinterpret_cast<uintptr_t>(exc_cell) & 15u) || !cell_state)
+    throw std::runtime_error("patched histogram: exception list (16-byte aligned) and cell table");
+  if (count_labels && total_bins < 1) throw std::runtime_error("patched histogram: no class-count column");
+  const PatchSpec ps{exc_cell, cell_state, n_exc};
+  switch (b) {
+#define AV_PATCHED(BB)                                                                                          \
+  case BB:                                                                                                      \
+    launch_joint_radix<BB, true>(dense, n, rs, (int)J, nfeat, n_classes, total_bins, count_labels, out, ps, stream); \
+    break;
+    AV_PATCHED(4) AV_PATCHED(5) AV_PATCHED(6) AV_PATCHED(7) AV_PATCHED(8) AV_PATCHED(9) AV_PATCHED(10) AV_PATCHED(11)
+    AV_PATCHED(12) AV_PATCHED(13) AV_PATCHED(14)
+#undef AV_PATCHED
+    default: throw std::runtime_error("patched histogram: 4..14 bits per record");
   }
 }
 

@@ -95,6 +95,13 @@ class RowPacked:
     dense_is_radix: bool = False        # ``dense`` holds mixed-radix codes, not the bit-field records
     field_bits: int | None = None       # bits of the bit-field record when ``bits`` counts the radix code
     bitfield: torch.Tensor | None = None  # the bit-field stream next to a radix ``dense`` (built on first use)
+    # the patched stream next to a radix ``dense`` (``attach_patched``; GPU only, None where it does not pay)
+    patched: torch.Tensor | None = None   # the records' cells, ``patched_bits`` each, in the container of ``dense``
+    patched_bits: int | None = None       # b < bits; ESC = 2^b - 1 marks a record listed in the exceptions
+    exc_index: torch.Tensor | None = None  # int64 [E], ascending: the records that store ESC
+    exc_cell: torch.Tensor | None = None   # int16 [E]: their cells (> ESC)
+    cell_state: torch.Tensor | None = None  # int16 [J + 1]: state of a cell, -1 for cell ESC
+    state_cell: torch.Tensor | None = None  # int16 [J]: cell of a state
 
     def ensure_dense(self) -> "RowPacked":
         """Attach the dense B-bit stream (32 records per B dwords) the joint-table kernels stream
@@ -112,6 +119,7 @@ class RowPacked:
                                                     int(self.label_shift), int(self.class_radix),
                                                     int(self.n_classes))
                 self.field_bits, self.bits, self.dense_is_radix = self.bits, int(B), True
+                attach_patched(self)
                 return self
         if 4 <= self.bits <= 15:
             self.dense = _native.C().pack_dense(self.words, int(self.n), int(self.bits))
@@ -148,6 +156,179 @@ def radix_layout(bins: Sequence[int], n_classes: int, missing: Sequence[bool] | 
     if not 4 <= B <= 15:
         return None
     return radices, class_radix, int(J), int(B), int(R)
+
+
+# ------------------------------------------------------------------------------------------------
+# patched record stream: b < B = ceil(log2 J) bits per record beside the B-bit mixed-radix stream.
+# A record whose state is among the 2^b - 1 most frequent stores that state's frequency rank; any
+# other stores ESC = 2^b - 1 and is listed as (record index, cell) in the exception lists.  The cell
+# of rank r is r below ESC and r + 1 from ESC on, so J + 1 cells (cell ESC a dummy) index one joint
+# table.  ``ref_patch_encode`` / ``ref_patch_decode`` define the format; the HIP packer equals them
+# bit for bit (tests/test_rowpack_patched.py).
+# ------------------------------------------------------------------------------------------------
+PATCH_SAMPLE = 1 << 20     # records of the strided sample the states are ranked from
+# A patched stream is kept while its kernel bytes (stream + 2 per exception) stay below PATCH_MARGIN
+# times the plain stream's.  profiles/patched_cap_sweep.jsonl (benchmarks/bench_patched_sweep.py, 2^28
+# churn-shaped records, 10 against 11 bits): patched won every repetition up to 2 % escaped records,
+# a byte ratio of 0.9372; at 4 % (0.9622) only the median won, at 8 % (1.0173) the plain stream did.
+PATCH_MARGIN = 0.937
+
+
+def patch_ranks(counts) -> torch.Tensor:
+    """int64 [J]: frequency rank of every state, by descending count, ties by ascending code."""
+    c = torch.as_tensor(counts, dtype=torch.int64).cpu()
+    order = torch.sort(-c, stable=True).indices
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(c.numel())
+    return rank
+
+
+def patch_tables(counts, b: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(state_cell int16 [J], cell_state int16 [J + 1]) at width b; cell ESC maps to no state (-1)."""
+    rank = patch_ranks(counts)
+    J, esc = rank.numel(), (1 << int(b)) - 1
+    if not 4 <= int(b) <= 14 or esc + 1 >= J or J + 1 > 1 << 15:
+        raise ValueError("patched stream: 4 <= b < ceil(log2 J), b <= 14, J + 1 <= 2^15")
+    state_cell = torch.where(rank < esc, rank, rank + 1)
+    cell_state = torch.full((J + 1,), -1, dtype=torch.int64)
+    cell_state[state_cell] = torch.arange(J)
+    return state_cell.to(torch.int16), cell_state.to(torch.int16)
+
+
+def patch_cost(counts, b: int) -> float:
+    """Estimated kernel bytes per record at width b: b / 8 + 2 p_exc(b)."""
+    c = torch.as_tensor(counts, dtype=torch.int64).cpu()
+    top = torch.sort(c, descending=True).values
+    return b / 8.0 + 2.0 * float(top[(1 << b) - 1:].sum()) / max(1, int(c.sum()))
+
+
+def choose_patch_bits(counts, margin: float = PATCH_MARGIN) -> int | None:
+    """The width b in [4, B - 1] of the least estimated bytes per record (the smaller b on a tie),
+    or None when no width stays below ``margin`` * B / 8 or the layout has no patched stream."""
+    J = int(torch.as_tensor(counts).numel())
+    B = max(0, J - 1).bit_length()
+    if J + 1 > 1 << 15 or int(torch.as_tensor(counts).sum()) <= 0:
+        return None
+    best = None
+    for b in range(4, min(B, 15)):
+        cost = patch_cost(counts, b)
+        if best is None or cost < best[0]:
+            best = (cost, b)
+    if best is None or not best[0] < margin * B / 8.0:
+        return None
+    return best[1]
+
+
+def patch_keep(b: int, B: int, n: int, n_exc: int, margin: float = PATCH_MARGIN) -> bool:
+    """The decision after packing, with the exact exception count: the kernel reads the stream and
+    two bytes per exception."""
+    groups = (int(n) + 31) // 32
+    return b * groups * 4 + 2 * int(n_exc) < margin * (B * groups * 4)
+
+
+def _pack_bits(v: torch.Tensor, B: int) -> torch.Tensor:
+    """int32 [ceil(n / 32) * B]: value k of group g at bits [k B, k B + B) of the group's B dwords."""
+    v = v.long().cpu()
+    n = v.numel()
+    r = torch.arange(n)
+    pos = (r // 32) * (32 * B) + (r % 32) * B
+    acc = torch.zeros((n + 31) // 32 * B, dtype=torch.int64)
+    for i in range(B):
+        acc.index_add_(0, (pos + i) // 32, ((v >> i) & 1) << ((pos + i) % 32))
+    return torch.where(acc >= 1 << 31, acc - (1 << 32), acc).to(torch.int32)
+
+
+def _unpack_bits(dense: torch.Tensor, n: int, B: int) -> torch.Tensor:
+    d = dense.long().cpu() & 0xFFFFFFFF
+    r = torch.arange(n)
+    pos = (r // 32) * (32 * B) + (r % 32) * B
+    v = torch.zeros(n, dtype=torch.int64)
+    for i in range(B):
+        v |= ((d[(pos + i) // 32] >> ((pos + i) % 32)) & 1) << i
+    return v
+
+
+def ref_patch_encode(code: torch.Tensor, state_cell: torch.Tensor, b: int):
+    """CPU twin of the packer: (stream int32, exc_index int64 ascending, exc_cell int16) of the
+    mixed-radix codes ``code`` int64 [n]."""
+    cell = state_cell.long().cpu()[code.long().cpu()]
+    esc = (1 << int(b)) - 1
+    out = cell > esc
+    stream = _pack_bits(torch.where(out, torch.full_like(cell, esc), cell), int(b))
+    return stream, out.nonzero().flatten(), cell[out].to(torch.int16)
+
+
+def ref_patch_decode(stream: torch.Tensor, n: int, b: int, exc_index: torch.Tensor, exc_cell: torch.Tensor,
+                     cell_state: torch.Tensor) -> torch.Tensor:
+    """Inverse of ``ref_patch_encode``: the int64 [n] mixed-radix codes."""
+    cell = _unpack_bits(stream, int(n), int(b))
+    esc = (1 << int(b)) - 1
+    idx = exc_index.long().cpu()
+    assert torch.equal((cell == esc).nonzero().flatten(), idx), "the exceptions are the records that store ESC"
+    cell[idx] = exc_cell.long().cpu() & 0xFFFF
+    return cell_state.long().cpu()[cell]
+
+
+def _radix_codes(rp: "RowPacked", words: torch.Tensor) -> torch.Tensor:
+    """int64 mixed-radix codes of 16-bit ``words`` in the layout of ``rp`` (as the packer kernels:
+    every digit clamped to its radix)."""
+    w = words.to(torch.int64) & 0xFFFF
+    code = torch.zeros_like(w)
+    mult = 1
+    if rp.class_radix > 1:
+        lb = (w >> rp.label_shift) & 3
+        cd = torch.where(lb == 1, torch.zeros_like(lb), torch.where(lb == 2, torch.ones_like(lb), torch.full_like(lb, 2)))
+        code = cd.clamp_max(rp.class_radix - 1)
+        mult = rp.class_radix
+    for s, wd, r in zip(rp.shifts, rp.widths, rp.radices):
+        code = code + ((w >> s) & ((1 << wd) - 1)).clamp_max(r - 1) * mult
+        mult *= r
+    return code
+
+
+def attach_patched(rp: "RowPacked", bits: int | None = None, sample: torch.Tensor | None = None,
+                   margin: float | None = None) -> "RowPacked":
+    """Build the patched stream of ``rp`` next to its mixed-radix stream (GPU only), or leave none
+    where it does not pay.  The states are ranked from a strided sample of at most PATCH_SAMPLE
+    records (``sample``: record indices to rank from instead); the width is ``choose_patch_bits``
+    of the sample and the stream is kept when ``patch_keep`` holds for the exact exception count.
+    ``bits`` forces a width and keeps the stream whatever it costs (tests, the margin sweep)."""
+    rp.patched = rp.patched_bits = rp.exc_index = rp.exc_cell = rp.cell_state = rp.state_cell = None
+    if not rp.dense_is_radix or not rp.words.is_cuda or rp.n <= 0:
+        return rp
+    margin = PATCH_MARGIN if margin is None else float(margin)
+    J = int(rp.class_radix)
+    for r in rp.radices:
+        J *= int(r)
+    B = int(rp.bits)
+    if B < 5 or J + 1 > 1 << 15:
+        return rp
+    picked = rp.words[:rp.n:-(-rp.n // PATCH_SAMPLE)] if sample is None else rp.words[sample]
+    counts = torch.bincount(_radix_codes(rp, picked), minlength=J).cpu()
+    if bits is None:
+        b = choose_patch_bits(counts, margin)
+        if b is None:
+            return rp
+    else:
+        b = int(bits)
+        if not 4 <= b < B:
+            raise ValueError("patched stream: 4 <= bits < ceil(log2 J)")
+    state_cell, cell_state = patch_tables(counts, b)
+    dev = rp.words.device
+    state_cell, cell_state = state_cell.to(dev), cell_state.to(dev)
+    lay = (int(rp.n), b, list(rp.shifts), list(rp.widths), list(rp.radices), list(rp.bins), int(rp.label_shift),
+           int(rp.class_radix), int(rp.n_classes), state_cell)
+    stream, n_exc = _native.C().pack_patched(rp.words, *lay)
+    E = int(n_exc.item())
+    if bits is None and not patch_keep(b, B, rp.n, E, margin):
+        return rp                        # the sample misled: the plain stream is the shorter read
+    idx, cell = _native.C().patch_exceptions(rp.words, *lay, E)
+    if E:                                # the kernel appends in any order: the same bits on every run
+        idx, order = torch.sort(idx)
+        cell = cell[order]
+    rp.patched, rp.patched_bits, rp.exc_index, rp.exc_cell = stream, b, idx, cell
+    rp.cell_state, rp.state_cell = cell_state, state_cell
+    return rp
 
 
 def rowpack_layout(bins: Sequence[int], n_classes: int, missing: Sequence[bool] | None = None):
@@ -234,9 +415,10 @@ def class_histogram_packed(rp: RowPacked, out: torch.Tensor | None = None,
                            count_labels: bool = False) -> torch.Tensor:
     """``class_histogram`` over row-packed records (same ``[C, sum(bins) (+1)]`` int64 result).
     GPU: the K2 joint-table kernel streams the records' dense stream (``ensure_dense``: mixed-radix
-    codes, else bit fields), or the 16-bit words, instead of F + 1 bytes of code columns;
-    AVMI_ROWPACK_KERNEL=bitfield / joint / nibble select the bit-field stream and the two word
-    kernels.  CPU: unpack + the column reference."""
+    codes, else bit fields; the patched stream where ``attach_patched`` kept one), or the 16-bit
+    words, instead of F + 1 bytes of code columns; AVMI_ROWPACK_KERNEL=radix / bitfield / joint /
+    nibble select the plain mixed-radix stream, the bit-field stream and the two word kernels.
+    CPU: unpack + the column reference."""
     C = rp.n_classes
     tb = sum(rp.bins) + (1 if count_labels else 0)
     if out is None:
@@ -252,12 +434,18 @@ def class_histogram_packed(rp: RowPacked, out: torch.Tensor | None = None,
         order = sorted(range(len(rp.bins)), key=lambda k: (C == 2 and rp.widths[k] > 2, k))
         dev = rp.words.device
         kind = os.environ.get("AVMI_ROWPACK_KERNEL", "dense")
-        if kind == "dense" and rp.dense_is_radix:
+        if kind == "dense" and rp.patched is not None:
+            # patched records: the same hot loop over fewer bits, the exception list added after it
+            _native.C().class_histogram_patched(rp.patched, int(rp.n), int(rp.patched_bits), list(rp.radices),
+                                                list(rp.bins), offs, int(rp.class_radix), tb, C, out,
+                                                bool(count_labels), rp.exc_cell, rp.cell_state)
+            return out
+        if kind in ("dense", "radix") and rp.dense_is_radix:
             # mixed-radix records: the code is the cell of the J-cell joint table, one LDS atomic per record
             _native.C().class_histogram_radix(rp.dense, int(rp.n), int(rp.bits), list(rp.radices), list(rp.bins),
                                               offs, int(rp.class_radix), tb, C, out, bool(count_labels))
             return out
-        stream = rp.ensure_bitfield() if kind in ("dense", "bitfield") else None
+        stream = rp.ensure_bitfield() if kind in ("dense", "radix", "bitfield") else None
         if stream is not None:
             # bit-field records back to back, one LDS atomic per record into the 2^bits joint table
             fb = rp.field_bits if rp.dense_is_radix else rp.bits
