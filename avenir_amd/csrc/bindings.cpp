@@ -1332,6 +1332,60 @@ void hmm_estep(const at::Tensor& obs, const at::Tensor& A, const at::Tensor& B, 
                  workspace.data_ptr<float>(), cur_stream(obs));
 }
 
+// DBSCAN (dbscan.hip).  metric 0: thr is the squared-distance threshold of eps_sq_threshold, 1:
+// manhattan, thr = float32(eps).  a_range (0 = default) forces the A rows per workgroup range.
+static void dbscan_check(const char* what, const at::Tensor& X, int64_t metric, double thr, int64_t a_range) {
+  CHECK_DEV(X);
+  CHECK_DTYPE(X, at::kFloat);
+  TORCH_CHECK(X.dim() == 2, what, ": rows must be [n, D]");
+  TORCH_CHECK(X.size(1) >= 1 && X.size(1) <= 64, what, ": 1 <= D <= 64");
+  TORCH_CHECK(X.size(0) < (1LL << 31), what, ": too many rows");
+  TORCH_CHECK(metric == 0 || metric == 1, what, ": metric 0 (euclidean) or 1 (manhattan)");
+  TORCH_CHECK(std::isfinite(thr) && thr >= 0.0 && (double)(float)thr == thr, what,
+              ": the threshold must be a finite fp32 value >= 0");
+  TORCH_CHECK(a_range >= 0 && a_range < (1LL << 31), what, ": 0 <= a_range < 2^31");
+}
+
+// counts int32 [n]: neighbours of every row of X (the row itself included)
+at::Tensor dbscan_count(const at::Tensor& X, int64_t metric, double thr, int64_t a_range) {
+  dbscan_check("dbscan_count", X, metric, thr, a_range);
+  DevGuard g(X.device());
+  auto counts = at::zeros({X.size(0)}, X.options().dtype(at::kInt));
+  avk::dbscan_count(X.data_ptr<float>(), X.size(0), (int)X.size(1), (int)metric, (float)thr, a_range,
+                    counts.data_ptr<int>(), cur_stream(X));
+  return counts;
+}
+
+// root int32 [nc]: the smallest row index of the connected component of every (core) row of Xc
+at::Tensor dbscan_union(const at::Tensor& Xc, int64_t metric, double thr, int64_t a_range) {
+  dbscan_check("dbscan_union", Xc, metric, thr, a_range);
+  DevGuard g(Xc.device());
+  auto parent = at::arange(Xc.size(0), Xc.options().dtype(at::kInt));
+  auto root = at::empty_like(parent);
+  avk::dbscan_union(Xc.data_ptr<float>(), Xc.size(0), (int)Xc.size(1), (int)metric, (float)thr, a_range,
+                    parent.data_ptr<int>(), root.data_ptr<int>(), cur_stream(Xc));
+  return root;
+}
+
+// min_root int32 [nb]: the smallest root among the core neighbours of every row of Xb, INT_MAX
+// where it has none
+at::Tensor dbscan_border(const at::Tensor& Xb, const at::Tensor& Xc, const at::Tensor& root, int64_t metric,
+                         double thr, int64_t a_range) {
+  dbscan_check("dbscan_border", Xb, metric, thr, a_range);
+  dbscan_check("dbscan_border", Xc, metric, thr, a_range);
+  CHECK_DEV(root);
+  CHECK_DTYPE(root, at::kInt);
+  TORCH_CHECK(Xb.size(1) == Xc.size(1), "dbscan_border: Xb and Xc must have the same D");
+  TORCH_CHECK(root.dim() == 1 && root.size(0) == Xc.size(0), "dbscan_border: root must be [nc]");
+  TORCH_CHECK(Xc.device() == Xb.device() && root.device() == Xb.device(),
+              "dbscan_border: every tensor must be on the device of Xb");
+  DevGuard g(Xb.device());
+  auto min_root = at::full({Xb.size(0)}, std::numeric_limits<int>::max(), Xb.options().dtype(at::kInt));
+  avk::dbscan_border(Xb.data_ptr<float>(), Xb.size(0), Xc.data_ptr<float>(), Xc.size(0), root.data_ptr<int>(),
+                     (int)Xb.size(1), (int)metric, (float)thr, a_range, min_root.data_ptr<int>(), cur_stream(Xb));
+  return min_root;
+}
+
 at::Tensor viterbi_chunks(const at::Tensor& obs, const at::Tensor& logA, const at::Tensor& logB,
                           const at::Tensor& logpi, int64_t n, int64_t obs_div, const c10::optional<at::Tensor>& bp) {
   CHECK_DEV(obs);
@@ -4834,6 +4888,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("viterbi", &viterbi);
   m.def("viterbi_chunks", &viterbi_chunks);
   m.def("hmm_estep", &hmm_estep);
+  m.def("dbscan_count", &dbscan_count, py::arg("X"), py::arg("metric"), py::arg("thr"), py::arg("a_range") = 0);
+  m.def("dbscan_union", &dbscan_union, py::arg("Xc"), py::arg("metric"), py::arg("thr"), py::arg("a_range") = 0);
+  m.def("dbscan_border", &dbscan_border, py::arg("Xb"), py::arg("Xc"), py::arg("root"), py::arg("metric"),
+        py::arg("thr"), py::arg("a_range") = 0);
   m.def("viterbi_backtrack", &viterbi_backtrack);
   m.def("markov_logodds", &markov_logodds);
   m.def("itemset_support", &itemset_support);

@@ -98,6 +98,20 @@ void hmm_estep(const short* obs, long long n, int T, int S, int O, const float* 
                const float* pi, unsigned long long* trans, unsigned long long* emit, unsigned long long* init,
                float* Z, int* E, unsigned long long* stats, float* workspace, hipStream_t stream);
 
+// ---- dbscan.hip ------------------------------------------------------------------------------
+// The predicate is s(i, j) <= thr with s the fp32 sum defined in models/dbscan.py (metric 0: squared
+// euclidean against the host's squared threshold, 1: manhattan).  1 <= D <= 64, rows < 2^31.
+// a_range: A rows per grid.y range (0 = chosen from the sizes); no result depends on it.
+// counts [n] (zero on entry) += neighbours of every row, the row itself included
+void dbscan_count(const float* X, long long n, int D, int metric, float thr, long long a_range, int* counts,
+                  hipStream_t stream);
+// parent [nc] holds the identity on entry; root[c] = smallest index of c's connected component
+void dbscan_union(const float* Xc, long long nc, int D, int metric, float thr, long long a_range, int* parent,
+                  int* root, hipStream_t stream);
+// min_root [nb] (INT_MAX on entry) = smallest root among the core neighbours of every candidate
+void dbscan_border(const float* Xb, long long nb, const float* Xc, long long nc, const int* root, int D, int metric,
+                   float thr, long long a_range, int* min_root, hipStream_t stream);
+
 // ---- assoc.hip (K17) -----------------------------------------------------------------------
 void itemset_support(const unsigned long long* P, int W, const unsigned long long* items,
                      const int* cand_prefix, const int* cand_item, int M, unsigned long long* support,
