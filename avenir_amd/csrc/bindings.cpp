@@ -1386,6 +1386,52 @@ at::Tensor dbscan_border(const at::Tensor& Xb, const at::Tensor& Xc, const at::T
   return min_root;
 }
 
+// Agglomerative clustering (agglo.hip).  The distance matrix of X [n, D]: M [n, ld] with ld = n rounded
+// up to 4 floats (16-byte row loads), and the largest off-diagonal entry as its int32 bit pattern.
+std::tuple<at::Tensor, int64_t> agglo_matrix(const at::Tensor& X, int64_t metric, bool take_sqrt) {
+  CHECK_DEV(X);
+  CHECK_DTYPE(X, at::kFloat);
+  TORCH_CHECK(X.dim() == 2 && X.size(0) >= 1, "agglo_matrix: rows must be [n >= 1, D]");
+  TORCH_CHECK(X.size(1) >= 1 && X.size(1) <= 64, "agglo_matrix: 1 <= D <= 64");
+  TORCH_CHECK(X.size(0) < (1LL << 24), "agglo_matrix: too many rows");
+  TORCH_CHECK(metric == 0 || metric == 1, "agglo_matrix: metric 0 (euclidean) or 1 (manhattan)");
+  DevGuard g(X.device());
+  const int64_t n = X.size(0), ld = (n + 3) / 4 * 4;
+  auto M = at::empty({n, ld}, X.options());
+  auto top = at::zeros({1}, X.options().dtype(at::kInt));
+  avk::agglo_matrix(X.data_ptr<float>(), n, (int)X.size(1), (int)metric, take_sqrt, M.data_ptr<float>(), ld,
+                    reinterpret_cast<unsigned*>(top.data_ptr<int>()), cur_stream(X));
+  return {M, top.item<int>()};
+}
+
+// The rounds on the M [n, ld] of agglo_matrix (destroyed).  Returns the
+// n - 1 merge records in no particular order (stored height, round, survivor, dead slot) and the
+// number of rounds.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, int64_t> agglo_merge(const at::Tensor& M, int64_t n,
+                                                                                int64_t linkage) {
+  CHECK_DEV(M);
+  CHECK_DTYPE(M, at::kFloat);
+  TORCH_CHECK(M.dim() == 2 && M.size(0) == n && n >= 1 && n < (1LL << 24), "agglo_merge: M must be [n, ld]");
+  TORCH_CHECK(M.size(1) == (n + 3) / 4 * 4, "agglo_merge: ld must be n rounded up to a multiple of 4");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(M.data_ptr()) % 16 == 0, "agglo_merge: M must be 16-byte aligned");
+  TORCH_CHECK(linkage >= 0 && linkage <= 3, "agglo_merge: linkage 0 single, 1 complete, 2 average, 3 ward");
+  DevGuard g(M.device());
+  const auto io = M.options().dtype(at::kInt);
+  auto key = at::empty({n}, M.options().dtype(at::kLong));
+  auto mate = at::full({n}, -1, io), size = at::ones({n}, io), pairs = at::zeros({n}, io);
+  auto act = at::zeros({2, n}, io);
+  act.select(0, 0).copy_(at::arange(n, io));
+  auto cnt = at::zeros({2 * n}, io);
+  auto h = at::empty({n - 1}, M.options());
+  auto rnd = at::empty({n - 1}, io), si = at::empty({n - 1}, io), sj = at::empty({n - 1}, io);
+  const int rounds = avk::agglo_merge(M.data_ptr<float>(), n, M.size(1), (int)linkage,
+                                      reinterpret_cast<unsigned long long*>(key.data_ptr<int64_t>()),
+                                      mate.data_ptr<int>(), size.data_ptr<int>(), act.data_ptr<int>(),
+                                      pairs.data_ptr<int>(), cnt.data_ptr<int>(), h.data_ptr<float>(),
+                                      rnd.data_ptr<int>(), si.data_ptr<int>(), sj.data_ptr<int>(), cur_stream(M));
+  return {h, rnd, si, sj, rounds};
+}
+
 at::Tensor viterbi_chunks(const at::Tensor& obs, const at::Tensor& logA, const at::Tensor& logB,
                           const at::Tensor& logpi, int64_t n, int64_t obs_div, const c10::optional<at::Tensor>& bp) {
   CHECK_DEV(obs);
@@ -4892,6 +4938,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("dbscan_union", &dbscan_union, py::arg("Xc"), py::arg("metric"), py::arg("thr"), py::arg("a_range") = 0);
   m.def("dbscan_border", &dbscan_border, py::arg("Xb"), py::arg("Xc"), py::arg("root"), py::arg("metric"),
         py::arg("thr"), py::arg("a_range") = 0);
+  m.def("agglo_matrix", &agglo_matrix, py::arg("X"), py::arg("metric"), py::arg("take_sqrt"));
+  m.def("agglo_merge", &agglo_merge, py::arg("M"), py::arg("n"), py::arg("linkage"));
   m.def("viterbi_backtrack", &viterbi_backtrack);
   m.def("markov_logodds", &markov_logodds);
   m.def("itemset_support", &itemset_support);

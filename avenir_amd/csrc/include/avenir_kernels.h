@@ -112,6 +112,20 @@ void dbscan_union(const float* Xc, long long nc, int D, int metric, float thr, l
 void dbscan_border(const float* Xb, long long nb, const float* Xc, long long nc, const int* root, int D, int metric,
                    float thr, long long a_range, int* min_root, hipStream_t stream);
 
+// ---- agglo.hip -------------------------------------------------------------------------------
+// Agglomerative clustering by rounds of reciprocal nearest pairs (models/agglo.py).  M [n][ld], ld a
+// multiple of 4 and >= n: the pair sums of dbscan.hip (metric 0 squared euclidean, 1 manhattan) or
+// their correctly rounded square roots, +inf on the diagonal and in the padding columns; top[0]
+// (zero on entry) = the largest off-diagonal bit pattern.  1 <= D <= 64, n < 2^24.
+void agglo_matrix(const float* X, long long n, int D, int metric, bool take_sqrt, float* M, long long ld,
+                  unsigned* top, hipStream_t stream);
+// linkage 0 single, 1 complete, 2 average, 3 ward (M holds squares).  On entry size [n] = 1, act
+// [2][n] = the identity in its first half, cnt [2 * n] = 0; key, mate, pairs [n] are scratch.  The
+// n - 1 merge records (stored height, round, survivor, dead slot) come out in any order.  Reads one
+// counter back per round and throws after n - 1 rounds; returns the number of rounds.
+int agglo_merge(float* M, long long n, long long ld, int linkage, unsigned long long* key, int* mate, int* size,
+                int* act, int* pairs, int* cnt, float* h, int* rnd, int* si, int* sj, hipStream_t stream);
+
 // ---- assoc.hip (K17) -----------------------------------------------------------------------
 void itemset_support(const unsigned long long* P, int W, const unsigned long long* items,
                      const int* cand_prefix, const int* cand_item, int M, unsigned long long* support,

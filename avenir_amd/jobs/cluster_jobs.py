@@ -9,8 +9,13 @@ P/unsupv/cluster.py driver, in the script's print formats.
 * ``common.mode=explore``, ``expl.algo=hopkins``: ``cluster.hopkins`` once per
   ``expl.hopkins.num.iters`` with seeds 0, 1, ..., and the mean.
 
-``train.algo=kmeans`` is the ``kmeansCluster`` verb; agglomerative clustering and
-``common.mode=predict`` are not supported.
+``train.algo=kmeans`` is the ``kmeansCluster`` verb and ``train.algo=agglomerative`` the
+``agglomerativeCluster`` verb below; ``common.mode=predict`` is not supported.
+
+``agglomerativeCluster <properties file> [key=value ...]`` reads the same file: the data keys above,
+the first entry of ``train.num.clusters``, ``train.affinity`` (``default`` means euclidean),
+``train.linkage`` and ``train.output.cluster.members``, and runs
+:class:`avenir_amd.models.agglo.AgglomerativeClustering` whatever ``common.mode`` and ``train.algo`` say.
 """
 from __future__ import annotations
 
@@ -55,6 +60,23 @@ def _train_dbscan(conf, X, out):
         if noise:
             out(f"noise points size {len(noise)}")
             out(str(noise))
+        for c in range(m.n_clusters_):
+            members = np.flatnonzero(labels == c).tolist()
+            out(f"cluster index {c}  size {len(members)}")
+            out(str(members))
+    out(f"num of clusters {m.n_clusters_}")
+
+
+def _train_agglomerative(conf, X, out):
+    from ..models.agglo import AgglomerativeClustering
+    k = int(str(_get(conf, "train.num.clusters", "2")).split(",")[0])
+    affinity, link = _get(conf, "train.affinity", "default"), _get(conf, "train.linkage", "default")
+    out("starting agglomerative clustering...")
+    m = AgglomerativeClustering(n_clusters=k, metric="euclidean" if affinity == "default" else affinity,
+                                linkage="ward" if link == "default" else link).fit(X)
+    labels = m.labels_.cpu().numpy()
+    out(str(labels.tolist()))
+    if _bool(conf, "train.output.cluster.members"):
         for c in range(m.n_clusters_):
             members = np.flatnonzero(labels == c).tolist()
             out(f"cluster index {c}  size {len(members)}")
@@ -114,4 +136,14 @@ def cluster_verb(args):
         (_expl_kdist if algo == "kdist" else _expl_hopkins)(conf, _data(rest[0], conf, dev), out)
     else:
         raise ValueError(f"unsupported mode {mode} (common.mode=train | explore)")
+    out.close()
+
+
+@job("agglomerativeCluster", "agglomerative clustering (P/unsupv/cluster.py, train.algo=agglomerative): "
+     "agglomerativeCluster <props> [key=value ...]; train.num.clusters, train.affinity, train.linkage")
+def agglomerative_cluster_verb(args):
+    rest = _rest(args, 1, "agglomerativeCluster <props> [key=value ...]")
+    conf, dev = _props(rest[0], rest[1:]), _dev(args)
+    out = _Out(args)
+    _train_agglomerative(conf, _data(rest[0], conf, dev), out)
     out.close()
