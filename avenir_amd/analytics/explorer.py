@@ -427,12 +427,12 @@ class DataExplorer:
         return {"numOutliers": int(m.sum()), "outliers": Xn[m], "dataWithoutOutliers": Xn[~m],
                 "outlierIndexes": np.nonzero(m)[0]}
 
-    def getOutliersWithIsoForest(self, contamination, *dsl, seed: int = 0):
+    def getOutliersWithIsoForest(self, contamination, *dsl, seed: int = 0, engine: str = "torch"):
         """Isolation forest over the named numeric data sets (P/mlextra/daexp.py:921-941)."""
         from ..models.outlier import IsolationForest
         assert 0 <= contamination <= 0.5, "contamination outside valid range"
         X = self._matrix(dsl)
-        iso = IsolationForest(contamination=contamination if contamination > 0 else "auto", seed=seed)
+        iso = IsolationForest(contamination=contamination if contamination > 0 else "auto", seed=seed, engine=engine)
         return self._outlier_result(X, iso.fit_predict(X) == -1)
 
     def getOutliersWithLocalFactor(self, dss, k: int = 10, contamination: float = 0.05):

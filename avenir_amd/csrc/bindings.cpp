@@ -1432,6 +1432,63 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, int64_t> agglo_merge(
   return {h, rnd, si, sj, rounds};
 }
 
+// Isolation forest (iforest.hip).  feat int32, thr fp32, size int32, each [T, M]: T trees of psi rows
+// sampled from X [n, D], tree ids tree_base .. tree_base + T - 1.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> iforest_build(const at::Tensor& X, int64_t n_trees, int64_t psi,
+                                                             uint64_t seed, uint64_t tree_base) {
+  CHECK_DEV(X);
+  CHECK_DTYPE(X, at::kFloat);
+  TORCH_CHECK(X.dim() == 2 && X.size(0) >= 1, "iforest_build: rows must be [n >= 1, D]");
+  TORCH_CHECK(X.size(1) >= 1 && X.size(1) <= 64, "iforest_build: 1 <= D <= 64");
+  TORCH_CHECK(X.size(0) < (1LL << 31), "iforest_build: too many rows");
+  TORCH_CHECK(psi >= 1 && psi <= 1024 && psi <= X.size(0), "iforest_build: 1 <= psi <= min(1024, n)");
+  TORCH_CHECK(n_trees >= 1 && n_trees < (1LL << 24), "iforest_build: 1 <= n_trees < 2^24");
+  DevGuard g(X.device());
+  int L = 1;
+  while ((1 << L) < psi) ++L;
+  const int64_t M = (2LL << L) - 1;
+  const auto io = X.options().dtype(at::kInt);
+  auto feat = at::empty({n_trees, M}, io), size = at::empty({n_trees, M}, io);
+  auto thr = at::empty({n_trees, M}, X.options());
+  avk::iforest_build(X.data_ptr<float>(), X.size(0), (int)X.size(1), (int)psi, (int)n_trees, seed, tree_base,
+                     feat.data_ptr<int>(), thr.data_ptr<float>(), size.data_ptr<int>(), cur_stream(X));
+  return {feat, thr, size};
+}
+
+// path fp32 [n]: the mean path length of every row of X [n, D] over the trees feat / thr / leaf_c
+// [T, M].  A feature outside [-1, D) raises.
+at::Tensor iforest_score(const at::Tensor& X, const at::Tensor& feat, const at::Tensor& thr,
+                         const at::Tensor& leaf_c) {
+  CHECK_DEV(X);
+  CHECK_DTYPE(X, at::kFloat);
+  CHECK_DEV(feat);
+  CHECK_DTYPE(feat, at::kInt);
+  for (const at::Tensor* t : {&thr, &leaf_c}) {
+    CHECK_DEV((*t));
+    CHECK_DTYPE((*t), at::kFloat);
+  }
+  TORCH_CHECK(X.dim() == 2, "iforest_score: rows must be [n, D]");
+  TORCH_CHECK(X.size(1) >= 1 && X.size(1) <= 64, "iforest_score: 1 <= D <= 64");
+  TORCH_CHECK(feat.dim() == 2 && feat.size(0) >= 1, "iforest_score: feat must be [T >= 1, M]");
+  const int64_t T = feat.size(0), M = feat.size(1);
+  int L = 1;
+  while (L <= 10 && (2LL << L) - 1 != M) ++L;
+  TORCH_CHECK(L <= 10, "iforest_score: M must be 2^(L+1) - 1 with 1 <= L <= 10 (psi <= 1024)");
+  TORCH_CHECK(T < (1LL << 24), "iforest_score: too many trees");
+  TORCH_CHECK(thr.sizes() == feat.sizes() && leaf_c.sizes() == feat.sizes(),
+              "iforest_score: thr and leaf_c must have the shape of feat");
+  TORCH_CHECK(feat.device() == X.device() && thr.device() == X.device() && leaf_c.device() == X.device(),
+              "iforest_score: every tensor must be on the device of X");
+  DevGuard g(X.device());
+  auto [fmin, fmax] = at::aminmax(feat);
+  TORCH_CHECK(fmin.item<int>() >= -1 && fmax.item<int>() < X.size(1), "iforest_score: feat outside [-1, D)");
+  auto nodes = at::stack({feat, at::where(feat >= 0, thr, leaf_c).view(at::kInt)}, 2).contiguous();
+  auto out = at::empty({X.size(0)}, X.options());
+  avk::iforest_score(X.data_ptr<float>(), X.size(0), (int)X.size(1), nodes.data_ptr<int>(), (int)T, L,
+                     out.data_ptr<float>(), cur_stream(X));
+  return out;
+}
+
 at::Tensor viterbi_chunks(const at::Tensor& obs, const at::Tensor& logA, const at::Tensor& logB,
                           const at::Tensor& logpi, int64_t n, int64_t obs_div, const c10::optional<at::Tensor>& bp) {
   CHECK_DEV(obs);
@@ -4940,6 +4997,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("thr"), py::arg("a_range") = 0);
   m.def("agglo_matrix", &agglo_matrix, py::arg("X"), py::arg("metric"), py::arg("take_sqrt"));
   m.def("agglo_merge", &agglo_merge, py::arg("M"), py::arg("n"), py::arg("linkage"));
+  m.def("iforest_build", &iforest_build, py::arg("X"), py::arg("n_trees"), py::arg("psi"), py::arg("seed"),
+        py::arg("tree_base"));
+  m.def("iforest_score", &iforest_score, py::arg("X"), py::arg("feat"), py::arg("thr"), py::arg("leaf_c"));
   m.def("viterbi_backtrack", &viterbi_backtrack);
   m.def("markov_logodds", &markov_logodds);
   m.def("itemset_support", &itemset_support);

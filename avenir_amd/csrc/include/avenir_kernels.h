@@ -126,6 +126,20 @@ void agglo_matrix(const float* X, long long n, int D, int metric, bool take_sqrt
 int agglo_merge(float* M, long long n, long long ld, int linkage, unsigned long long* key, int* mate, int* size,
                 int* act, int* pairs, int* cnt, float* h, int* rnd, int* si, int* sj, hipStream_t stream);
 
+// ---- iforest.hip -----------------------------------------------------------------------------
+// The deterministic isolation forest of models/iforest.py.  Trees are heap-indexed, M = 2^(L+1) - 1
+// nodes with L = max(1, ceil(log2(max(psi, 2)))).
+// Grows T trees (ids tree_base .. tree_base + T - 1) from psi sampled rows each, one workgroup per
+// tree, and writes every node of feat / thr / size [T][M].  1 <= psi <= min(1024, n), 1 <= D <= 64,
+// n < 2^31.  X must be finite.
+void iforest_build(const float* X, long long n, int D, int psi, int T, unsigned long long seed,
+                   unsigned long long tree_base, int* feat, float* thr, int* size, hipStream_t stream);
+// out [n] = mean path length of every row.  nodes [T][M][2]: the feature or -1, then the bits of
+// the threshold (inner node) or of leaf_c (leaf); a feature outside [-1, D) is read as a leaf.
+// 1 <= L <= 10, 1 <= D <= 64.
+void iforest_score(const float* X, long long n, int D, const int* nodes, int T, int L, float* out,
+                   hipStream_t stream);
+
 // ---- assoc.hip (K17) -----------------------------------------------------------------------
 void itemset_support(const unsigned long long* P, int W, const unsigned long long* items,
                      const int* cand_prefix, const int* cand_item, int M, unsigned long long* support,

@@ -18,6 +18,13 @@ with trees x nodes.
 ``contamination="auto"`` puts the offset at -0.5, as scikit-learn does; a number sets it at that
 percentile of the training scores.  The random draws differ from scikit-learn's, so the parity
 is statistical (outlier sets overlap on planted-outlier data; see tests/test_outlier.py).
+
+``engine="torch"`` (the default) is the forest described above; its draws come from
+``torch.Generator``, so a CPU and a GPU fit of one seed are different forests.  ``engine="philox"``
+is the deterministic forest of ``models/iforest.py``: every draw is Philox, the forest is a pure
+function of ``(X, n_estimators, psi, seed, tree_base)``, one kernel launch grows it and one scores a
+batch (csrc/kernels/iforest.hip), and the numpy twin gives the same bits on the CPU.  ``use_kernel``
+(``None | True | False``) forces that engine's choice between the kernels and the twin.
 """
 from __future__ import annotations
 
@@ -39,14 +46,18 @@ def avg_path_length(n: torch.Tensor) -> torch.Tensor:
 
 class IsolationForest:
     def __init__(self, n_estimators: int = 100, max_samples: int | str = "auto",
-                 contamination: float | str = "auto", seed: int = 0, chunk: int = 1 << 16):
+                 contamination: float | str = "auto", seed: int = 0, chunk: int = 1 << 16,
+                 engine: str = "torch", use_kernel=None):
+        if engine not in ("torch", "philox"):
+            raise ValueError("engine must be torch or philox")
+        self.engine, self.use_kernel = engine, use_kernel
         self.n_estimators = int(n_estimators)
         self.max_samples = max_samples
         self.contamination = contamination
         self.seed = int(seed)
         self.chunk = int(chunk)
 
-    def fit(self, X) -> "IsolationForest":
+    def fit(self, X, tree_base: int = 0) -> "IsolationForest":
         X = torch.as_tensor(X).float()
         if X.dim() == 1:
             X = X.unsqueeze(1)
@@ -58,6 +69,10 @@ class IsolationForest:
         L = max(1, math.ceil(math.log2(max(psi, 2))))
         self.depth = L
         T = self.n_estimators
+        if self.engine == "philox":
+            return self._fit_philox(X, int(tree_base))
+        if tree_base:
+            raise ValueError("tree_base belongs to engine=philox")
         g = torch.Generator(device=dev)
         g.manual_seed(self.seed)
         if n <= (1 << 20):
@@ -114,11 +129,31 @@ class IsolationForest:
             self.offset_ = float(np.percentile(train.double().cpu().numpy(), 100.0 * c))
         return self
 
+    def _fit_philox(self, X: torch.Tensor, tree_base: int) -> "IsolationForest":
+        """The deterministic forest of models/iforest.py: the kernels for a CUDA tensor within their
+        limits, the numpy twin otherwise (on a host copy of a CUDA tensor), the same bits either
+        way.  With ``contamination="auto"`` the training set is not scored."""
+        from . import iforest
+        if self.contamination != "auto" and not 0.0 < float(self.contamination) <= 0.5:
+            raise ValueError("contamination must be in (0, 0.5]")
+        self.feat, self.thr, self.size, self.leaf_c = iforest.build(
+            X, self.n_estimators, self.psi, self.seed, tree_base, self.use_kernel)
+        self.c_psi = float(avg_path_length(torch.tensor(float(self.psi))))
+        if self.contamination == "auto":
+            self.offset_ = -0.5
+        else:
+            train = self.score_samples(X)
+            self.offset_ = float(np.percentile(train.double().cpu().numpy(), 100.0 * float(self.contamination)))
+        return self
+
     def path_length(self, X) -> torch.Tensor:
         """Mean isolation depth over the trees (with the leaf-size correction), [n]."""
         X = torch.as_tensor(X).float().to(self.feat.device)
         if X.dim() == 1:
             X = X.unsqueeze(1)
+        if self.engine == "philox":
+            from . import iforest
+            return iforest.path_length(X, self.feat, self.thr, self.leaf_c, self.psi, self.use_kernel)
         T = self.feat.shape[0]
         out = []
         for s in range(0, X.shape[0], self.chunk):
